@@ -10,6 +10,10 @@ statistics are all-reduced — the intra-node data plane that replaces the refer
 part upload to the stitcher (reference worker/tasks.py:1655-1674).
 
     python bench.py --gpus N --steps K --warmup W [--res 1080p|4k] [--batch B] [--gop G]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line; ``--full`` adds the
+4K pass of the default 1080p run (``fps_4k`` ... in ``config``).  ``--dump-outputs DIR`` writes
+what the last timed step returned as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -177,6 +181,44 @@ def _timed(args, step, dev, world, post, extra_ranks=None):
     return float(el_t.item()), step_ms, res, ranks
 
 
+DUMP_CAP = 3_500_000  # elements per dumped array; at most four large arrays -> < 64 MB of float32
+
+
+def _dump_sample(a, seed: int):
+    """float32 copy of `a` (flattened if sampled): whole up to DUMP_CAP elements, else the
+    elements at DUMP_CAP sorted positions drawn from a generator seeded by `seed` and the
+    array's length — the same positions in every run that produces the same length."""
+    import numpy as np
+
+    a = np.asarray(a)
+    if a.size > DUMP_CAP:
+        idx = np.sort(np.random.default_rng([seed, a.size]).integers(0, a.size, DUMP_CAP))
+        a = a.reshape(-1)[idx]
+    return a.astype(np.float32)
+
+
+def _dump_outputs(out_dir: str, segs, sse=None, recon=None) -> None:
+    """--dump-outputs: what the last timed step returned to its caller on this rank, as
+    float32 / float64 .npy files — per segment the bitstream length, its CRC-32 and the
+    reconstruction SSE (Y, U, V), the concatenated bitstream bytes and, where the engine
+    exposes it, the last reconstructed picture of segment 0 (large arrays as a fixed seeded
+    sample, _dump_sample)."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"segment_bytes": np.array([len(x) for x in segs], np.float64),
+           "segment_crc32": np.array([zlib.crc32(x) for x in segs], np.float64),
+           "bitstream": _dump_sample(np.frombuffer(b"".join(segs), np.uint8), 1)}
+    if sse is not None:
+        out["sse"] = np.asarray(sse, np.float64)
+    for name, plane in zip(("recon_y", "recon_u", "recon_v"), recon or ()):
+        out[name] = _dump_sample(plane, 2)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def ladder_main(args) -> None:
     """BASELINE config #5 on N GPUs: each rank pushes `batch` segments x `gop` frames of a
     seeded synthetic HDR10 (P010, PQ) source through tone-map -> every rung's Lanczos
@@ -222,9 +264,13 @@ def ladder_main(args) -> None:
         i = counter[0]
         counter[0] += 1
         segs = lad.encode_overlapped(batch, i % 2, prepare_next=lambda: prep(i + 1))
+        last["segs"] = segs
         post.submit(comm, segs)
 
+    last = {}
     el, step_ms, res, ranks = _timed(args, step, dev, world, post, [len(cpus), lad.engines[0].threads])
+    if args.dump_outputs and rank == 0:  # rung-major: every rung's segments of the last step
+        _dump_outputs(args.dump_outputs, [x for r in last["segs"] for x in r])
     tot = np.sum(res, axis=0)
     q = lad.psnr()
     if rank == 0:
@@ -463,11 +509,13 @@ def av1_main(args) -> None:
         g = gfut.result()  # decisions on the host (copy stream, behind the next GOP's kernels)
         sse = g.sse.sum(axis=(0, 1)).astype(np.float64)
         segs = [b"".join(f.result()) for f in eng.submit_entropy(g)]
+        last.update(segs=segs, sse=g.sse)
         stats = torch.tensor([batch * args.gop, sum(len(x) for x in segs), *sse], dtype=torch.float64, device=dev)
         dist.all_reduce(stats)
         gathered = gather_bytes_to_root(b"".join(segs), dev)
         return stats.cpu().numpy(), (sum(len(x) for x in gathered) if gathered else 0)
 
+    last = {}
     pass1_bits = []
     gathered_mb = lambda res: round(sum(r[1] for r in res) / 1e6, 6)  # noqa: E731
     from thinvids_amd.models.ratecontrol import BatchRateController
@@ -560,6 +608,8 @@ def av1_main(args) -> None:
                                       lambda: COMM_STATS["p2p_recv_bytes"] - c0["p2p_recv_bytes"]])
     for f in plans.values():  # the look-ahead pass 1 of the step after the last one
         f.result()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, last["segs"], last["sse"])
     tot = np.sum([r[0] for r in res], axis=0)
     frames = tot[0]
     npx = frames * w * h
@@ -658,7 +708,12 @@ def main() -> None:
     ap.add_argument("--codec", default="hevc", choices=["hevc", "av1"], help="av1: BASELINE config #4 engine")
     ap.add_argument("--qindex", type=int, default=0, help="AV1 q-index (0 = matched to --qp)")
     ap.add_argument("--kbps", type=float, default=0.0, help="2-pass rate control to this kbps per 30 fps stream")
-    ap.add_argument("--no-4k", action="store_true", help="skip the 4K pass of the default 1080p run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the 4K pass after the default 1080p run")
+    ap.add_argument("--no-4k", action="store_true", help="with --full: skip the 4K pass of the default 1080p run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned on rank 0 (bitstreams, SSE, last "
+                         "reconstructed picture) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
     ap.add_argument("--no-wpp", dest="wpp", action="store_false",
                     help="one CABAC substream per slice (coded on the host) instead of WPP rows coded on the GPU")
     ap.add_argument("--no-rqt", dest="rqt", action="store_false", help="HEVC: no residual quadtree")
@@ -676,6 +731,8 @@ def main() -> None:
         args.res = "tiny" if args.cpu else "1080p"
     if args.src is None:
         args.src = "tiny" if args.cpu else "8k"
+    if args.job and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes a step bench's last step; the job bench publishes its output as a file")
     if args.cpu and args.job:
         raise SystemExit("--cpu rehearses the step benches; the job bench runs the node executor (tests cover it on CPU)")
     if args.cpu and args.range == 64:
@@ -704,7 +761,7 @@ def main() -> None:
         import copy
 
         a4 = copy.copy(args)
-        a4.res, a4.batch = "4k", 0
+        a4.res, a4.batch, a4.dump_outputs = "4k", 0, None
         o4 = hevc_pass(a4, world, rank, local, dev, cpus)
         if rank == 0:
             c4 = o4["config"]
@@ -717,8 +774,8 @@ def main() -> None:
 
 
 def _with_4k(args) -> bool:
-    """The default driver run (1080p, shipped config, constant QP) also reports 4K."""
-    return (not args.no_4k and not args.cpu and args.res == "1080p" and args.kbps <= 0
+    """With --full, the default run (1080p, shipped config, constant QP) also reports 4K."""
+    return (args.full and not args.no_4k and not args.cpu and args.res == "1080p" and args.kbps <= 0
             and args.bframes == _WORKER_BFRAMES and args.content == "smooth")
 
 
@@ -812,10 +869,16 @@ def hevc_pass(args, world, rank, local, dev, cpus):
             first[i + 1] = pre.submit(eng1.encode_synthetic, starts_of(i + 1))
             qm = post.ex.submit(plan_pass2, i, first.pop(i).result()).result()
             segs = eng.encode_synthetic(starts_of(i), qp=qm)
-            post.submit(comm_rc, i, segs, np.array([eng.sse(b) for b in range(batch)]).sum(0))
+            sse = np.array([eng.sse(b) for b in range(batch)])
+            last.update(segs=segs, sse=sse)
+            post.submit(comm_rc, i, segs, sse.sum(0))
             return
         segs = eng.encode_synthetic(starts_of(s))
-        post.submit(comm, segs, np.array([eng.sse(b) for b in range(batch)]).sum(0))
+        sse = np.array([eng.sse(b) for b in range(batch)])
+        last.update(segs=segs, sse=sse)
+        post.submit(comm, segs, sse.sum(0))
+
+    last = {}  # what the latest step returned (--dump-outputs)
 
     from thinvids_amd.parallel.comm import COMM_STATS
 
@@ -825,6 +888,9 @@ def hevc_pass(args, world, rank, local, dev, cpus):
                                       lambda: COMM_STATS["p2p_recv_bytes"] - c0["p2p_recv_bytes"]])
     for f in first.values():  # the look-ahead pass 1 of the step after the last one
         f.result()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, last["segs"], last["sse"],
+                      eng.last_recon(0) if hasattr(eng, "last_recon") else None)
     tot = np.sum([r[0] for r in res], axis=0)
     gathered_bytes = sum(r[1] for r in res)
     frames = tot[0]

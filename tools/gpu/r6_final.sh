@@ -11,7 +11,7 @@ rc=$?; echo "pytest rc=$rc"; tail -n 2 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit 
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; echo "smoke rc=$rc"; [ $rc -eq 0 ] || exit $rc
 run() { n=$1; shift; timeout -k 10 600 python -u bench.py "$@" > $O/$n.log 2>&1 || { echo "$n failed"; tail -n 5 $O/$n.log; exit 1; }
   python3 -c "import json; L=[l for l in open('$O/$n.log') if l.startswith('{')]; r=json.loads(L[-1]); c=r['config']; print('$n', r['value'], c.get('fps_4k'), c.get('psnr_y_db'), c.get('kbps_per_30fps_stream'))"; }
-run bench --steps 10 --warmup 3
+run bench --full --steps 10 --warmup 3
 run bench_gpuent --no-4k --steps 6 --warmup 2 --entropy gpu
 run bench_b8 --no-4k --steps 6 --warmup 2 --bframes 8
 run bench_av1_4k --codec av1 --res 4k --steps 4 --warmup 2

@@ -5,7 +5,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp PYTHONPATH=$PWD
 O=gpurun_out/${1:-gap}; mkdir -p $O
-timeout -k 10 400 python -u bench.py --steps 8 --warmup 2 > $O/default.log 2>&1
+timeout -k 10 400 python -u bench.py --full --steps 8 --warmup 2 > $O/default.log 2>&1
 rc=$?; echo "default rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/default.log; exit $rc; }
 python3 -c "import json; r=json.loads([l for l in open('$O/default.log') if l.startswith('{')][-1]); c=r['config']; print('default', r['value'], 'fps_4k', c.get('fps_4k'), c['per_rank_cpu'][0], c['entropy'], c['step_ms'], c.get('step_ms_4k'))"
 timeout -k 10 400 python -u bench.py --steps 8 --warmup 2 --res 4k > $O/4k.log 2>&1
