@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "hsa_dma.h"
 #include "k_encode.h"
 #include "tv/me_model.h"
 #include "tv/cpu_encoder.h"
@@ -53,14 +54,14 @@ namespace gpu {
 // blit kernel (`__amd_rocclr_copyBuffer`: 6.7 % of the 1080p bench's kernel time, CUs taken
 // from the analysis kernels).  The fetch thread has already waited for the slot's event, so
 // the copies need no stream ordering; it blocks on one completion signal per batch.
-// TV_D2H=hip keeps the HIP path (also the fallback when no CPU agent is found).
+// The HIP path is the fallback when no CPU agent is found.
 class SdmaD2H {
  public:
   static SdmaD2H& get() {
     static SdmaD2H s;
     return s;
   }
-  bool on() const { return on_; }
+  bool on() const { return cpu_.handle != 0; }
   struct Batch {
     std::vector<std::pair<void*, std::pair<const void*, size_t>>> items;
     void add(void* dst, const void* src, size_t n) {
@@ -70,48 +71,35 @@ class SdmaD2H {
   // every copy of the batch, then wait for all of them
   void run(const Batch& b) {
     if (b.items.empty()) return;
-    hsa_signal_t sig;
-    if (hsa_signal_create((hsa_signal_value_t)b.items.size(), 0, nullptr, &sig) != HSA_STATUS_SUCCESS)
-      throw std::runtime_error("hsa_signal_create failed");
+    HsaSignal sig((hsa_signal_value_t)b.items.size());
+    if (!sig.ok()) throw std::runtime_error("hsa_signal_create failed");
+    size_t queued = 0;
+    const char* err = nullptr;
     for (const auto& it : b.items) {
       hsa_amd_pointer_info_t info{};
       info.size = sizeof(info);
       if (hsa_amd_pointer_info(it.second.first, &info, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS ||
           info.type != HSA_EXT_POINTER_TYPE_HSA) {
-        hsa_signal_destroy(sig);
-        throw std::runtime_error("SDMA D2H: source is not HSA device memory");
+        err = "SDMA D2H: source is not HSA device memory";
+        break;
       }
       if (hsa_amd_memory_async_copy(it.first, cpu_, it.second.first, info.agentOwner, it.second.second, 0, nullptr,
-                                    sig) != HSA_STATUS_SUCCESS) {
-        hsa_signal_destroy(sig);
-        throw std::runtime_error("hsa_amd_memory_async_copy failed");
+                                    sig.get()) != HSA_STATUS_SUCCESS) {
+        err = "hsa_amd_memory_async_copy failed";
+        break;
       }
+      ++queued;
     }
-    while (hsa_signal_wait_scacquire(sig, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED) >= 1) {
-    }
-    hsa_signal_destroy(sig);
+    // a copy that was never queued never counts the signal down: take those off, so the wait
+    // covers exactly the copies in flight (they write into the caller's buffers)
+    if (queued < b.items.size()) sig.drop((hsa_signal_value_t)(b.items.size() - queued));
+    sig.wait();
+    if (err) throw std::runtime_error(err);
   }
 
  private:
-  SdmaD2H() {
-    const char* e = getenv("TV_D2H");
-    if (e && std::string(e) == "hip") return;
-    hsa_iterate_agents(
-        [](hsa_agent_t a, void* data) {
-          hsa_device_type_t t;
-          if (hsa_agent_get_info(a, HSA_AGENT_INFO_DEVICE, &t) == HSA_STATUS_SUCCESS && t == HSA_DEVICE_TYPE_CPU) {
-            *static_cast<hsa_agent_t*>(data) = a;
-            return HSA_STATUS_INFO_BREAK;
-          }
-          return HSA_STATUS_SUCCESS;
-        },
-        &cpu_);
-    on_ = cpu_.handle != 0;
-  }
-  hsa_agent_t cpu_{0};
-  bool on_ = false;
+  const hsa_agent_t cpu_ = hsa_cpu_agent();
 };
-
 
 // ROCTx ranges (TV_ROCTX=1): host-side frame / D2H / entropy stages appear next to the
 // kernels in `rocprofv3 --marker-trace --kernel-trace` timelines.
@@ -1215,7 +1203,6 @@ class Engine {
       for (auto& core : cores_) core->init_entropy_stream(l);
   }
   ~Engine() {
-    intra_timing_report();
     cores_.clear();
     pool_.reset();
   }

@@ -31,8 +31,6 @@ void launch_gather_frames(const uint8_t* frames, long seg_stride, FrameSet src, 
 // n slice QPs from host memory into device memory as kernel arguments (no blit copy)
 void launch_set_qp(int8_t* dst, const int8_t* host, int n, hipStream_t s);
 void launch_sse(FrameSet a, FrameSet r, const Geo& g, unsigned long long* sse, int B, hipStream_t s);
-bool intra_timing();
-void intra_timing_report();
 void launch_intra_frame(FrameSet src, FrameSet rec, DecisionSet dec, const Geo& g, const RcTables* rc, int B,
                         hipStream_t s);
 // Hierarchical motion-search state of one P frame (tv/me_model.h): quarter-res source luma

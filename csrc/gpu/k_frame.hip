@@ -1,6 +1,5 @@
 // k_frame.hip — frame-level kernels: synthetic source, PSNR SSE, quarter-pel phase planes,
 // in-loop deblocking.  Batched: blockIdx.z (or .y) selects the segment.
-#include <cstdlib>
 #include <cstring>
 
 #include "gpu_common.h"
@@ -522,7 +521,7 @@ __device__ __forceinline__ void sao_tile_pos(int i, int& c, int& j) {
 }
 
 __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, FrameSet out, uint32_t* sao, Geo g,
-                                                    const int8_t* qp, const RcTables* rc, int diag,
+                                                    const int8_t* qp, const RcTables* rc,
                                                     unsigned long long* sse) {
   const int tid = threadIdx.x, lane = tid & 63;
   int ctu, b;
@@ -596,9 +595,7 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
   // neighbour dwords of a pair read once for all 4 classes).  Edge CTBs take the per-sample
   // path with the validity checks.  Both give the same counters.
   static_assert(!kSaoBandOffsets, "the packed statistics carry no band histogram");
-  const bool packed = !(diag & 16);  // 16: TV_SAO_PACKED=0 (A/B: per-sample statistics and filter)
-  const bool interior = cx > 0 && cy > 0 && cx < g.wc - 1 && cy < g.hc - 1 && packed;
-  diag &= 15;
+  const bool interior = cx > 0 && cy > 0 && cx < g.wc - 1 && cy < g.hc - 1;
   const int piters = c ? 2 : 4;  // pairs per lane: luma 16 rows x 16 pairs, chroma 16 x 8
   int sv[8] = {};
   uint32_t sp[4] = {};
@@ -617,12 +614,6 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
     }
   }
   __syncthreads();
-  // timing diagnostics only (TV_DIAG_SAO_STOP=1/2/3: stop after staging / statistics /
-  // decision; the output is then incomplete) -- never set in production
-  if (diag == 1) {
-    if (tid == 0) sao[3 * ((long)b * g.wc * g.hc + ctu)] = (uint32_t)(sv[0] + sp[0] + tile[tid]);
-    return;
-  }
   int eo[4][4];
   if (interior) {
     const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
@@ -764,10 +755,6 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
     st[cc].bo_s[band] = (tot - (tot & 2047)) / 2048;
   }
   __syncthreads();
-  if (diag == 2) {
-    if (tid == 0) sao[3 * ((long)b * g.wc * g.hc + ctu)] = (uint32_t)st[0].eo_n[0][1];
-    return;
-  }
   // 144 offset/cost items in parallel (the 96 band items only with band offsets on)
   if (tid < kSaoItems && (kSaoBandOffsets || tid % 48 < 16)) sao_item(st, lam16, tid, tab);
   __syncthreads();
@@ -797,7 +784,6 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
     o[1] = prm[1];
     o[2] = prm[2];
   }
-  if (diag == 3) return;
   __syncthreads();
   // the SAO'd CTB from the tile, 4 samples per dword store: luma 32 rows x 8, chroma 16 x 4;
   // the squared error against the source (display area) is summed on the way (no k_sse).
@@ -819,56 +805,42 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
     const bool want_sse = sse && cy * nn + ly < dhc;
     const uint32_t sw = want_sse ? *reinterpret_cast<const uint32_t*>(src.plane(cc, b, g) + at) : 0u;
     uint32_t word = 0;
-    if (packed) {
-      const int i0 = sao_tix(cc, ly + 1, lx0 + 1) >> 1;  // pairs (lx0, lx0 + 1), (lx0 + 2, lx0 + 3)
-      const uint32_t C0 = tile32[i0], C1 = tile32[i0 + 1];
-      if (sao_type(p) == 2) {
-        int dx, dy;
-        sao_eo_dir(sao_class(p), dx, dy);
-        const int pd = (cc ? kSaoPc : kSaoP) >> 1;  // dwords per tile row
-        const int ra = i0 + dy * pd, rb = i0 - dy * pd;
-        const uint32_t Wa[4] = {tile32[ra - 1], tile32[ra], tile32[ra + 1], tile32[ra + 2]};
-        const uint32_t Wb[4] = {tile32[rb - 1], tile32[rb], tile32[rb + 1], tile32[rb + 2]};
-        // pair k of a row shifted by s columns (s = -1, 0, 1): dwords W[k .. k + 2] = columns
-        // lx0 + 2k - 2 .. lx0 + 2k + 3
-        auto shifted = [](const uint32_t* W, int k, int s) -> uint32_t {
-          return s == 0 ? W[k + 1] : s < 0 ? __builtin_amdgcn_alignbyte(W[k + 1], W[k], 2)
-                                           : __builtin_amdgcn_alignbyte(W[k + 2], W[k + 1], 2);
-        };
-        // biased offsets (o + 8) by category index e + 2: bytes {o0, o1, 8 (none), o2 | o3}
-        const uint32_t t0 = ((p >> 7) & 15) | ((p >> 11) & 15) << 8 | 8u << 16 | ((p >> 15) & 15) << 24;
-        const uint32_t t1 = (p >> 19) & 15;
-        const sao_s2 two = {2, 2}, eight = {8, 8};
-        const sao_u2 u8s = {8, 8};
-        uint32_t r2[2];
+    const int i0 = sao_tix(cc, ly + 1, lx0 + 1) >> 1;  // pairs (lx0, lx0 + 1), (lx0 + 2, lx0 + 3)
+    const uint32_t C0 = tile32[i0], C1 = tile32[i0 + 1];
+    if (sao_type(p) == 2) {
+      int dx, dy;
+      sao_eo_dir(sao_class(p), dx, dy);
+      const int pd = (cc ? kSaoPc : kSaoP) >> 1;  // dwords per tile row
+      const int ra = i0 + dy * pd, rb = i0 - dy * pd;
+      const uint32_t Wa[4] = {tile32[ra - 1], tile32[ra], tile32[ra + 1], tile32[ra + 2]};
+      const uint32_t Wb[4] = {tile32[rb - 1], tile32[rb], tile32[rb + 1], tile32[rb + 2]};
+      // pair k of a row shifted by s columns (s = -1, 0, 1): dwords W[k .. k + 2] = columns
+      // lx0 + 2k - 2 .. lx0 + 2k + 3
+      auto shifted = [](const uint32_t* W, int k, int s) -> uint32_t {
+        return s == 0 ? W[k + 1] : s < 0 ? __builtin_amdgcn_alignbyte(W[k + 1], W[k], 2)
+                                         : __builtin_amdgcn_alignbyte(W[k + 2], W[k + 1], 2);
+      };
+      // biased offsets (o + 8) by category index e + 2: bytes {o0, o1, 8 (none), o2 | o3}
+      const uint32_t t0 = ((p >> 7) & 15) | ((p >> 11) & 15) << 8 | 8u << 16 | ((p >> 15) & 15) << 24;
+      const uint32_t t1 = (p >> 19) & 15;
+      const sao_s2 two = {2, 2}, eight = {8, 8};
+      const sao_u2 u8s = {8, 8};
+      uint32_t r2[2];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const sao_s2 v = sao_pair(k ? C1 : C0);
-          const sao_s2 A = sao_pair(shifted(Wa, k, dx)), B = sao_pair(shifted(Wb, k, -dx));
-          const sao_s2 inv = (A | B) >> 15;  // -1 where a neighbour is outside the picture
-          const sao_s2 e = (sao_sign2(v - A) + sao_sign2(v - B)) & ~inv;
-          const uint32_t sel = __builtin_bit_cast(uint32_t, e + two) | 0x0c000c00u;
-          const sao_s2 off = sao_pair(__builtin_amdgcn_perm(t1, t0, sel));
-          const sao_s2 r = sao_relu2(v + off - eight);  // -7 .. 262 -> 0 .. 262
-          // >= 256 -> low byte 0xFF (only the low byte of each half is kept)
-          r2[k] = __builtin_bit_cast(uint32_t, r | (sao_s2{0, 0} - __builtin_bit_cast(sao_s2, __builtin_bit_cast(sao_u2, r) >> u8s)));
-        }
-        word = __builtin_amdgcn_perm(r2[1], r2[0], 0x06040200u);
-      } else {
-        word = __builtin_amdgcn_perm(C1, C0, 0x06040200u);
+      for (int k = 0; k < 2; ++k) {
+        const sao_s2 v = sao_pair(k ? C1 : C0);
+        const sao_s2 A = sao_pair(shifted(Wa, k, dx)), B = sao_pair(shifted(Wb, k, -dx));
+        const sao_s2 inv = (A | B) >> 15;  // -1 where a neighbour is outside the picture
+        const sao_s2 e = (sao_sign2(v - A) + sao_sign2(v - B)) & ~inv;
+        const uint32_t sel = __builtin_bit_cast(uint32_t, e + two) | 0x0c000c00u;
+        const sao_s2 off = sao_pair(__builtin_amdgcn_perm(t1, t0, sel));
+        const sao_s2 r = sao_relu2(v + off - eight);  // -7 .. 262 -> 0 .. 262
+        // >= 256 -> low byte 0xFF (only the low byte of each half is kept)
+        r2[k] = __builtin_bit_cast(uint32_t, r | (sao_s2{0, 0} - __builtin_bit_cast(sao_s2, __builtin_bit_cast(sao_u2, r) >> u8s)));
       }
+      word = __builtin_amdgcn_perm(r2[1], r2[0], 0x06040200u);
     } else {
-      int dx = 0, dy = 0;
-      if (sao_type(p) == 2) sao_eo_dir(sao_class(p), dx, dy);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int lx = lx0 + q;
-        const int v = tile[sao_tix(cc, ly + 1, lx + 1)];
-        const int r = sao_type(p) ? sao_sample_nb(v, tile[sao_tix(cc, ly + 1 + dy, lx + 1 + dx)],
-                                                  tile[sao_tix(cc, ly + 1 - dy, lx + 1 - dx)], p)
-                                  : v;
-        word |= (uint32_t)r << (8 * q);
-      }
+      word = __builtin_amdgcn_perm(C1, C0, 0x06040200u);
     }
     *reinterpret_cast<uint32_t*>(out.plane(cc, b, g) + at) = word;
     if (want_sse) {
@@ -905,12 +877,7 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
 
 void launch_sao(FrameSet src, FrameSet deb, FrameSet out, uint32_t* sao, const int8_t* qp, const RcTables* rc,
                 const Geo& g, int B, hipStream_t s, unsigned long long* sse) {
-  static const int diag = [] {
-    const char* e = std::getenv("TV_DIAG_SAO_STOP");
-    const char* pk = std::getenv("TV_SAO_PACKED");
-    return (e ? std::atoi(e) : 0) | (pk && std::atoi(pk) == 0 ? 16 : 0);
-  }();
-  k_sao_decide<<<dim3(g.wc * g.hc, B), 256, 0, s>>>(src, deb, out, sao, g, qp, rc, diag, sse);
+  k_sao_decide<<<dim3(g.wc * g.hc, B), 256, 0, s>>>(src, deb, out, sao, g, qp, rc, sse);
 }
 
 void launch_deblock(FrameSet rec, DecisionSet dec, const Geo& g, int B, hipStream_t s) {

@@ -13,9 +13,7 @@
 //                   * bottom-up CU split decision.
 //  k_inter_recon  pass B per CTB: luma prediction = phase-plane loads, chroma 4-tap MC,
 //                 residual, MFMA transform/quant, exact inverse, reconstruction.
-#include <cstdlib>
 #include <stdexcept>
-#include <string>
 
 #include "gpu_common.h"
 #include "k_encode.h"
@@ -219,24 +217,19 @@ __global__ void __launch_bounds__(64) k_coarse_me(const uint8_t* qcur, const uin
   }
 }
 
-// ROWS: rows per sub-pel SAD group, 8 (384 groups) or 4 (768 groups, 3 per thread: measured
-// 10 % slower -- a third pass exposes its load latency once more).  PEN_LDS: the MV-rate table
-// (Penalties::mv, 64 ints) staged in LDS -- the integer search and the sub-pel argmin read it
-// per candidate, which from global memory put a dependent load chain between the barriers.
-// WPE: waves per SIMD the register allocation must allow (8: <= 64 VGPRs, 8 CTBs per CU --
-// with the 7.8 KB quadrant table gone the LDS fits 8 as well; 7 = the compiler's own 70 VGPRs).
-template <int ROWS, bool PEN_LDS, int WPE>
-__global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_inter_me(FrameSet src, FrameSet ref, const uint8_t* phase,
+// The MV-rate table (Penalties::mv, 64 ints) is staged in LDS: the integer search and the
+// sub-pel argmin read it per candidate.  8 waves per SIMD (<= 64 VGPRs): the LDS fits 8 CTBs
+// per CU as well.
+__global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) k_inter_me(FrameSet src, FrameSet ref, const uint8_t* phase,
                                                          DecisionSet dec, const int16_t* prev_mv, const int16_t* cmv,
-                                                         Geo g, const RcTables* rc, int range, int diag_stop,
+                                                         Geo g, const RcTables* rc, int range,
                                                          CtbMeOut* bout, PIntraBuffers pi) {
   const int tid = threadIdx.x;
   int ctu, b;
   xcd_ctb(ctu, b);
   const Penalties& pen = rc->pen[dec.qp[b]];
-  __shared__ int penL[64];
-  if (PEN_LDS && tid < 64) penL[tid] = pen.mv[tid];
-  const int* penmv = PEN_LDS ? penL : pen.mv;  // visible after the first barrier below
+  __shared__ int penmv[64];  // visible after the first barrier below
+  if (tid < 64) penmv[tid] = pen.mv[tid];
   const int cxi = ctu % g.wc, cyi = ctu / g.wc, cx = cxi * 32, cy = cyi * 32;
   const uint8_t* S = src.plane(0, b, g);
   const uint8_t* R = ref.plane(0, b, g);
@@ -270,14 +263,8 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   }
   if (tid < 21) best[tid] = 0xffffffffu;
   __syncthreads();
-  if (tid == 0) {
-    if (diag_stop & 16)  // TV_ME_CAND=global (A/B reference): the former global-memory path
-      ncand = me_candidates(cmv + (long)b * g.wc * g.hc * 2, g.wc, g.hc, cxi, cyi, tmv[0], tmv[1], range - 4, cand, pmv);
-    else
-      ncand = me_candidates(nbmv, lw, lh, cxi - lx0, cyi - ly0, tmv[0], tmv[1], range - 4, cand, pmv);
-  }
+  if (tid == 0) ncand = me_candidates(nbmv, lw, lh, cxi - lx0, cyi - ly0, tmv[0], tmv[1], range - 4, cand, pmv);
   __syncthreads();
-  diag_stop &= 15;
   const int nc = ncand;
   // candidate windows, each pre-aligned so byte 0 of a row is x = cx + cand_x + kMeWinX0
   // one lane per 16-byte chunk: a dwordx4 + dword load from the dword-aligned address, then
@@ -326,9 +313,6 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
     }
   }
   __syncthreads();
-  // timing diagnostics only (TV_DIAG_ME_STOP=1/2/3): later search phases are skipped and the
-  // decisions degrade (still well-formed); never set in production
-  const bool skip_int = diag_stop == 1, skip_sub = diag_stop == 1 || diag_stop == 2;
 
   // ------------------------------- integer refinement -----------------------------------
   // item = (candidate, window row, 4-position group, 16x16 quadrant): a lane accumulates
@@ -342,7 +326,7 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   for (int k = 0; k < 5; ++k) lb[k] = 0xffffffffu;
   unsigned lb32 = 0xffffffffu;  // the 32x32 minimum (quadrant-0 lanes)
   int qd = 0;
-  for (int item = skip_int ? kMeThreads * 64 : tid; item < nc * kMeWinH * 2 * 4; item += kMeThreads) {
+  for (int item = tid; item < nc * kMeWinH * 2 * 4; item += kMeThreads) {
     qd = item & 3;
     const int it = item >> 2;
     const int k = it / (kMeWinH * 2), rr = it - k * (kMeWinH * 2);
@@ -426,8 +410,8 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   __syncthreads();
   if (tid < 21) {
     int mx = 0, my = 0;
-    if (!skip_int) me_pos_to_mv((int)(best[tid] & 2047), cand, mx, my);
-    bcost[tid] = skip_int ? 0 : (int)(best[tid] >> 11);
+    me_pos_to_mv((int)(best[tid] & 2047), cand, mx, my);
+    bcost[tid] = (int)(best[tid] >> 11);
     bmv[tid][0] = 4 * mx;
     bmv[tid][1] = 4 * my;
   }
@@ -435,25 +419,25 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   // ------------------------ half- then quarter-pel refinement ---------------------------
   const uint8_t* sb = reinterpret_cast<const uint8_t*>(s32);
   const uint8_t* ph = phase + (long)b * 16 * g.psz;
-  const int last_step = skip_sub ? 4 : (diag_stop == 3 ? 2 : 1);
-  for (int step = 2; step >= last_step; step >>= 1) {
+#pragma unroll 1  // two passes of one loop body: unrolled, the kernel grows by a third and runs slower
+  for (int step = 2; step >= 1; step >>= 1) {
     __syncthreads();  // bmv of the previous step / the integer search
-    // A thread owns a group of ROWS rows x 8 pixels of one (block, candidate): per row it
+    // A thread owns a group of 8 rows x 8 pixels of one (block, candidate): per row it
     // loads 3 aligned dwords of the phase plane, forms the 2 shifted dwords with v_alignbyte
-    // and accumulates with v_sad_u8.  ROWS = 4: 32 (8x8) + 32 (16x16) + 32 (32x32) groups per
-    // candidate, 768 in all = exactly 3 per thread; ROWS = 8: 384 = 1.5 per thread (half the
-    // threads run a second pass while the others wait at the barrier).
-    constexpr int G8 = 8 / ROWS, N8 = 16 * G8, NC = 3 * N8;  // groups per 8x8 block / class / candidate
+    // and accumulates with v_sad_u8.  16 (8x8) + 16 (16x16) + 16 (32x32) groups per candidate,
+    // 384 in all = 1.5 per thread (half the threads run a second pass while the others wait
+    // at the barrier).
+    constexpr int ROWS = 8, N8 = 16, NC = 3 * N8;  // rows per group, groups per class / candidate
     for (int grp = tid; grp < 8 * NC; grp += kMeThreads) {
       const int k = grp / NC, r = grp - k * NC;
       int bi, row0, col0;
       if (r < N8) {
-        bi = r / G8;
-        row0 = ROWS * (r % G8);
+        bi = r;
+        row0 = 0;
         col0 = 0;
       } else if (r < 2 * N8) {
-        const int q = (r - N8) % (4 * G8);
-        bi = 16 + (r - N8) / (4 * G8);
+        const int q = (r - N8) % 4;
+        bi = 16 + (r - N8) / 4;
         row0 = ROWS * (q >> 1);
         col0 = 8 * (q & 1);
       } else {
@@ -493,22 +477,18 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
           }
         }
       }
-      // group sums on the VALU (a wave's lanes all run the same passes): aligned groups of G8
-      // lanes = an 8x8 block, 4 G8 = a 16x16 block, 16 G8 = the 32x32 block -- every
+      // group sums on the VALU (a wave's lanes all run the same passes): a lane = an 8x8
+      // block, an aligned group of 4 lanes = a 16x16 block, of 16 = the 32x32 block -- every
       // (block, candidate) cell is written exactly once, by a plain store
-      int s1 = (int)sad;
-      if (G8 == 2) s1 += dpp::mov<dpp::kQuadXor1>(s1);
-      int s4 = s1 + dpp::mov<G8 == 2 ? dpp::kQuadXor2 : dpp::kQuadXor1>(s1);
-      if (G8 == 1) s4 += dpp::mov<dpp::kQuadXor2>(s4);
-      else s4 += dpp::mov<dpp::kRowHalfMirror>(s4);  // G8 = 2: 8 lanes
-      int s16 = s4;
-      if (G8 == 1) s16 += dpp::mov<dpp::kRowHalfMirror>(s16);
+      const int s1 = (int)sad;
+      int s4 = s1 + dpp::mov<dpp::kQuadXor1>(s1);
+      s4 += dpp::mov<dpp::kQuadXor2>(s4);
+      int s16 = s4 + dpp::mov<dpp::kRowHalfMirror>(s4);
       s16 += dpp::mov<dpp::kRowMirror>(s16);
-      if (G8 == 2) s16 += __shfl_xor(s16, 16, 64);
       if (r < N8) {
-        if (r % G8 == 0) subsad[bi][k] = s1;
+        subsad[bi][k] = s1;
       } else if (r < 2 * N8) {
-        if ((r - N8) % (4 * G8) == 0) subsad[bi][k] = s4;
+        if ((r - N8) % 4 == 0) subsad[bi][k] = s4;
       } else if (r == 2 * N8) {
         subsad[bi][k] = s16;
       }
@@ -761,23 +741,19 @@ __device__ __forceinline__ bool pr_zeroed(const PReconLds& L, int id) {
   return L.nz[id] == 0 || (L.nz[id] == 1 && L.sa[id] == 1 && L.dc[id] == 0);
 }
 
-// WPE: waves per SIMD the register allocation must allow (6: 80 VGPRs; 7: 72, no scratch;
-// 8: 64 + a 36-byte spill since the packed prediction) -- TV_RECON_WPE for same-box A/B,
-// default 7 (+1.9 % over 8 at 1080p, profiles/r6_recon/).
-template <int WPE>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_inter_recon(FrameSet src, FrameSet ref, const uint8_t* phase,
-                                                     FrameSet rec, DecisionSet dec, Geo g, int tile_skip,
+// 7 waves per SIMD: 72 VGPRs and no scratch (8 would need 64 and spills).
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) k_inter_recon(FrameSet src, FrameSet ref, const uint8_t* phase,
+                                                     FrameSet rec, DecisionSet dec, Geo g,
                                                      FrameSet ref1, const uint8_t* phase1) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int diag = (tile_skip >> 8) & 255;  // TV_DIAG_RECON_STOP (timing only)
-  const int rdoq = g.rdoq;                  // RDOQ-lite mode (tv code_tb), 0 off
-  tile_skip &= 255;
+  const int rdoq = g.rdoq;  // RDOQ-lite mode (tv code_tb), 0 off
   int ctu, b;
   xcd_ctb(ctu, b);
   const int qp = dec.qp[b];
   const int cx = (ctu % g.wc) * 32, cy = (ctu / g.wc) * 32;
   const long ub = b * g.usz;
   const int qpc = chroma_qp(qp, 0), Wc = g.W >> 1, Hc = g.H >> 1;
+  const long W = g.W;  // the luma pitch, widened once up here (stays scalar: no spill at 72 VGPRs)
   __shared__ PReconLds L;
   for (int i = tid; i < 1024; i += 256) L.T[i >> 5][i & 31] = (int16_t)kDct32.m[i >> 5][i & 31];
   if (tid < 16) {
@@ -830,7 +806,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
 #pragma unroll
           for (int k = 0; k < 4; ++k) pw |= (uint32_t)phase_at(P, g, px + k, cy + y + (mvy >> 2)) << (8 * k);
         }
-        const uint32_t sw = *reinterpret_cast<const uint32_t*>(S + (long)(cy + y) * g.W + cx + x);
+        const uint32_t sw = *reinterpret_cast<const uint32_t*>(S + (cy + y) * W + cx + x);
         *reinterpret_cast<uint32_t*>(&L.predY[y * 32 + x]) = pw;
         *reinterpret_cast<uint2*>(&L.resY[y * 32 + x]) = bytes_minus(sw, pw);
       }
@@ -884,7 +860,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
       const int x = (un & 3) * 8 + (lane & 7), y = (un >> 2) * 8 + (lane >> 3);
       const int p = bipred_sample(pl[0], pl[1]);
       L.predY[y * 32 + x] = (uint8_t)p;
-      L.resY[y * 32 + x] = (int16_t)((int)S[(long)(cy + y) * g.W + cx + x] - p);
+      L.resY[y * 32 + x] = (int16_t)((int)S[(cy + y) * W + cx + x] - p);
     }
     // chroma: one item = 4 samples of a row of one 4x4 unit (128 items), the separable 4-tap
     // filter on packed bytes: per reference row the 7 samples are two dwords, each output a
@@ -985,8 +961,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
   // tile t: luma (whole: 32x32 tile ti,tj = t>>1, t&1; else quadrant t) for t < 4, chroma
   // (whole: plane t-4 as one 16x16 TB; else the Cb|Cr pair of quadrant t-4) for t >= 4.
   // ---------------------------------------------------------------- stage 1: T * R
-  // (diag 1: no forward transform -- every TB counts as empty, the stream stays consistent)
-  for (int t = wave; t < (diag == 1 ? 0 : ntiles); t += 4) {
+  for (int t = wave; t < ntiles; t += 4) {
     int o[4];
     if (t < 4) {
       if (whole) {
@@ -1040,7 +1015,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
     }
     if (origin) L.dc[id] = lev;
   };
-  for (int t = wave; t < (diag == 1 ? 0 : ntiles); t += 4) {
+  for (int t = wave; t < ntiles; t += 4) {
     int o[4];
     if (t < 4) {
       if (whole) {
@@ -1091,7 +1066,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
   // per TB) and its diagonal is >= rdoq_dmin.  One thread per 4x4 group (luma 64, Cb / Cr 16).
   // A CTB whose TBs hold at most one level each skips it (workgroup-uniform): a lone level
   // the pass could drop is dropped by the whole-TB rule (pr_zeroed) anyway.
-  if (diag != 1 && rdoq && L.multi) {
+  if (rdoq && L.multi) {
     int code = 0, key = 0, id = 0, dmin = 1 << 20;
     int16_t* p = nullptr;
     int st = 32;
@@ -1141,12 +1116,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
   // ---- final levels (dropped TBs zeroed) -> the level planes; cbf per CU
   {
     // 4 levels (one TB: TBs are >= 4 wide and 4-aligned) per item, one 8-byte store
-    int16_t* LY = dec.coef_y + b * g.ysz + (long)cy * g.W + cx;
+    int16_t* LY = dec.coef_y + b * g.ysz + cy * W + cx;
     {
       const int x = (tid & 7) * 4, y = tid >> 3;
       uint2* r = reinterpret_cast<uint2*>(&L.resY[y * 32 + x]);
       if (pr_zeroed(L, pr_tb_luma(L, x, y))) *r = make_uint2(0u, 0u);
-      *reinterpret_cast<uint2*>(LY + (long)y * g.W + x) = *r;
+      *reinterpret_cast<uint2*>(LY + y * W + x) = *r;
     }
     if (tid < 128) {
       const int pl = tid >> 6, y = (tid >> 2) & 15, x = (tid & 3) * 4;
@@ -1166,7 +1141,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
         for (int pl = 0; pl < 2; ++pl)
           for (int k = 0; k < 4; ++k) z = z && pr_zeroed(L, pr_tb_chroma(L, pl, (q & 1) * 8 + (k & 1) * 4, (q >> 1) * 8 + (k >> 1) * 4));
       }
-      L.tzero[tid] = z && tile_skip;
+      L.tzero[tid] = z;
     }
     if (tid < 16) {
       const int x = (tid & 3) * 8, y = (tid >> 2) * 8;  // this unit's CU = its TBs
@@ -1176,7 +1151,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
     }
   }
   __syncthreads();
-  if (diag == 3) return;
   // --------------------------------------- stage 3: T^T * dequant(levels)  (split d)
   const DeqParams dq5 = deq_params(qp, 5), dqc4 = deq_params(qpc, 4);
   for (int t = wave; t < ntiles; t += 4) {
@@ -1221,7 +1195,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
     }
   }
   __syncthreads();
-  if (diag == 4) return;
   // ------------------------------------- stage 4: G * T + prediction -> reconstruction
   for (int t = wave; t < ntiles; t += 4) {
     int o[4];
@@ -1238,11 +1211,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
         if (!tz) mfma_tile([&](int r, int k) { return L.tmpY[(oy + r) * 33 + ox + k]; },
                   [&](int k, int c) { return pr_comp(L, l2, k, c); }, 0, 0, 16, true, true, o);
       }
-      uint8_t* R = rec.plane(0, b, g) + (long)cy * g.W + cx;
+      uint8_t* R = rec.plane(0, b, g) + cy * W + cx;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int y = (t >> 1) * 16 + (lane >> 4) * 4 + r, x = (t & 1) * 16 + (lane & 15);
-        R[(long)y * g.W + x] = (uint8_t)clip_pixel((int)L.predY[y * 32 + x] + ((o[r] + 2048) >> 12));
+        R[y * W + x] = (uint8_t)clip_pixel((int)L.predY[y * 32 + x] + ((o[r] + 2048) >> 12));
       }
     } else if (whole) {
       const int pl = t - 4;
@@ -1312,62 +1285,15 @@ void launch_rc_crf(const uint8_t* q, const int* ccost, int8_t* qp, const Geo& g,
   k_rc_crf<<<B, 256, 0, s>>>(q, ccost, qp, g, crf, intra ? 1 : 0);
 }
 
-// TV_RECON_TILE_SKIP=0 runs the inverse transform on all-zero tiles too (same output; kept
-// as a same-box A/B switch for the skip)
-static int recon_tile_skip() {
-  static const int v = [] {
-    const char* e = std::getenv("TV_RECON_TILE_SKIP");
-    // timing diagnostics only (TV_DIAG_RECON_STOP=1: no forward transform (all TBs empty), 3:
-    // stop after the level write, 4: after inverse stage 1; the reconstruction is then
-    // incomplete) -- never in production
-    const char* d = std::getenv("TV_DIAG_RECON_STOP");
-    return (e ? std::atoi(e) : 1) | (d ? (std::atoi(d) & 15) << 8 : 0);
-  }();
-  return v;
-}
-
-using ReconKernel = decltype(&k_inter_recon<7>);
-static ReconKernel recon_kernel() {
-  static const ReconKernel k = [] {
-    const char* e = std::getenv("TV_RECON_WPE");
-    const int w = e ? std::atoi(e) : 7;
-    return w == 6 ? &k_inter_recon<6> : (w == 8 ? &k_inter_recon<8> : &k_inter_recon<7>);
-  }();
-  return k;
-}
-
-// Variants for same-box A/B measurements (same decisions): TV_ME_SUBPEL_ROWS=4 (768 sub-pel
-// groups), TV_ME_PEN=global (MV-rate table read from global memory), TV_ME_WPE=7 (the
-// compiler's register allocation: 7 CTBs per CU).
-using MeKernel = decltype(&k_inter_me<8, true, 8>);
-static MeKernel me_kernel() {
-  static const MeKernel k = [] {
-    const char* r = std::getenv("TV_ME_SUBPEL_ROWS");
-    const char* p = std::getenv("TV_ME_PEN");
-    const char* w = std::getenv("TV_ME_WPE");
-    const bool rows4 = r && std::atoi(r) == 4, glob = p && std::string(p) == "global", w7 = w && std::atoi(w) == 7;
-    if (rows4) return glob ? &k_inter_me<4, false, 8> : &k_inter_me<4, true, 8>;
-    if (w7) return glob ? &k_inter_me<8, false, 7> : &k_inter_me<8, true, 7>;
-    return glob ? &k_inter_me<8, false, 8> : &k_inter_me<8, true, 8>;
-  }();
-  return k;
-}
-
 void launch_inter_frame(FrameSet src, FrameSet ref, const uint8_t* phase, FrameSet rec, DecisionSet dec,
                         const Geo& g, const RcTables* rc, int range, const MeBuffers& me, int B, hipStream_t s,
                         const PIntraBuffers* pi) {
-  static const int diag_stop = [] {
-    const char* e = std::getenv("TV_DIAG_ME_STOP");
-    const char* c = std::getenv("TV_ME_CAND");
-    return (e ? std::atoi(e) : 0) | (c && std::string(c) == "global" ? 16 : 0);
-  }();
   const PIntraBuffers none{};
   if (pi && hipMemsetAsync(pi->count, 0, 6 * sizeof(int), s) != hipSuccess) return;
-  me_kernel()<<<dim3(g.wc * g.hc, B), kMeThreads, 0, s>>>(src, ref, phase, dec, me.prev_mv, me.cmv, g, rc, range,
-                                                         diag_stop, nullptr, pi ? *pi : none);
+  const dim3 grid(g.wc * g.hc, B);
+  k_inter_me<<<grid, kMeThreads, 0, s>>>(src, ref, phase, dec, me.prev_mv, me.cmv, g, rc, range, nullptr, pi ? *pi : none);
   if (pi) launch_pintra_decide(src, dec, g, rc, *pi, B, s);
-  recon_kernel()<<<dim3(g.wc * g.hc, B), 256, 0, s>>>(src, ref, phase, rec, dec, g, recon_tile_skip(), FrameSet{},
-                                                     nullptr);
+  k_inter_recon<<<grid, 256, 0, s>>>(src, ref, phase, rec, dec, g, FrameSet{}, nullptr);
   if (pi) launch_pintra_recon(src, rec, dec, g, *pi, B, s);
 }
 
@@ -1377,10 +1303,10 @@ void launch_inter_frame_b(FrameSet src, FrameSet ref0, const uint8_t* phase0, Fr
   const dim3 grid(g.wc * g.hc, B);
   CtbMeOut* o1 = meout + (long)B * g.wc * g.hc;
   const PIntraBuffers none{};
-  me_kernel()<<<grid, kMeThreads, 0, s>>>(src, ref0, phase0, dec, me0.prev_mv, me0.cmv, g, rc, range[0], 0, meout, none);
-  me_kernel()<<<grid, kMeThreads, 0, s>>>(src, ref1, phase1, dec, me1.prev_mv, me1.cmv, g, rc, range[1], 0, o1, none);
+  k_inter_me<<<grid, kMeThreads, 0, s>>>(src, ref0, phase0, dec, me0.prev_mv, me0.cmv, g, rc, range[0], meout, none);
+  k_inter_me<<<grid, kMeThreads, 0, s>>>(src, ref1, phase1, dec, me1.prev_mv, me1.cmv, g, rc, range[1], o1, none);
   k_bi_decide<<<grid, 256, 0, s>>>(src, phase0, phase1, meout, o1, dec, g, rc);
-  recon_kernel()<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, recon_tile_skip(), ref1, phase1);
+  k_inter_recon<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, ref1, phase1);
 }
 
 }  // namespace gpu

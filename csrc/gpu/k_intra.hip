@@ -7,9 +7,6 @@
 //                    Then the bottom-up CU split decision.
 //  k_intra_recon     pass B, CTB anti-diagonal wavefront (cx + 2*cy = d per launch): the
 //                    normative prediction from reconstructed neighbours + MFMA TB coding.
-#include <cstdio>
-#include <cstdlib>
-
 #include "gpu_common.h"
 #include "k_encode.h"
 #include "tb_coder.h"
@@ -202,12 +199,8 @@ struct CompLdsT {
 };
 using CompLds = CompLdsT<32>;
 
-// TV_DIAG_INTRA=1: lane 0 of every wave adds the clock cycles of each phase to
-// g_intra_phase[c][phase] (c = component wave): timing only, printed at engine teardown.
-__device__ unsigned long long g_intra_phase[3][8];
-
 __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec, DecisionSet dec, Geo g, int diag,
-                                                     int cy0, int timing) {
+                                                     int cy0) {
   const int b = blockIdx.y, c = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int qp = dec.qp[b];
   __shared__ int Tm[32][33];
@@ -218,13 +211,6 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
   ang.load(threadIdx.x, 192);
   __shared__ int ncu;
   __shared__ unsigned cbfs[16];
-  long long tph = timing ? (long long)clock64() : 0;
-  auto mark = [&](int ph) {
-    if (!timing) return;
-    const long long t = (long long)clock64();
-    if ((threadIdx.x & 63) == 0) atomicAdd(&g_intra_phase[threadIdx.x >> 6][ph], (unsigned long long)(t - tph));
-    tph = t;
-  };
   const int cyi = cy0 + blockIdx.x, cxi = diag - 2 * cyi;
   const int cx = cxi * 32, cy = cyi * 32;
   const long ub = b * g.usz;
@@ -276,7 +262,6 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
     for (int i = lane; i < S; i += 64) L.left[i] = Rp[(long)tv_min(ph - 1, by + i) * pw + tv_max(0, bx - 1)];
   }
   __syncthreads();
-  mark(0);  // matrix + CU list + staging
   const int qpx = c ? chroma_qp(qp, 0) : qp;
   int16_t* coefp = (c == 0 ? dec.coef_y + b * g.ysz : (c == 1 ? dec.coef_u : dec.coef_v) + b * g.csz);
   for (int k = 0; k < ncu; ++k) {
@@ -314,7 +299,6 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
     if (total > 64) m[1] = round(1);
     if (total > 128) m[2] = round(2);
     wave_sync();
-    mark(1);  // reference samples + availability
     // --- substitution (H.265 8.4.4.2.2) as a parallel nearest-available search
     for (int i = lane; i < total; i += 64) {
       int j = -1;
@@ -332,7 +316,6 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
       else L.T[i - 2 * N] = v;
     }
     wave_sync();
-    mark(2);  // substitution
     const bool filt = c == 0 && intra_filter_refs(l2, mode);
     if (filt) {
       for (int i = lane; i <= 2 * N; i += 64) {
@@ -359,14 +342,11 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
       L.resid[i] = (int16_t)((int)L.src[(y - by + py) * S + (x - bx + px)] - p);
     }
     wave_sync();
-    mark(3);  // filter + prediction + residual
     const int cb = wave_code_tb(L.resid, L.pred, l2, qpx, true, coefp + (long)y * pw + x, pw,
                                 &L.rec[(y - by) * S + (x - bx)], S, Tm, L.tb);
     if (lane == 0 && cb) atomicOr(&cbfs[k], 1u << c);
-    mark(4);  // transform / quant / inverse / recon
   }
   __syncthreads();
-  mark(5);  // waiting for the other component waves
   // write the CTB reconstruction and the per-CU cbf flags back
   uint8_t* Rp = rec.plane(c, b, g) + (long)by * pw + bx;
   for (int i = lane; i < S * S; i += 64) Rp[(long)(i / S) * pw + i % S] = L.rec[i];
@@ -388,7 +368,7 @@ void launch_intra_frame(FrameSet src, FrameSet rec, DecisionSet dec, const Geo& 
     const int cy0 = tv_max(0, (d - (g.wc - 1) + 1) / 2);
     const int cy1 = tv_min(g.hc - 1, d / 2);
     if (cy1 < cy0) continue;
-    k_intra_recon<<<dim3(cy1 - cy0 + 1, B), 192, 0, s>>>(src, rec, dec, g, d, cy0, intra_timing() ? 1 : 0);
+    k_intra_recon<<<dim3(cy1 - cy0 + 1, B), 192, 0, s>>>(src, rec, dec, g, d, cy0);
   }
 }
 
@@ -624,26 +604,6 @@ void launch_pintra_decide(FrameSet src, DecisionSet dec, const Geo& g, const RcT
 void launch_pintra_recon(FrameSet src, FrameSet rec, DecisionSet dec, const Geo& g, const PIntraBuffers& pi, int B,
                          hipStream_t s) {
   for (int q = 0; q < 4; ++q) k_pintra_recon<<<128, 192, 0, s>>>(src, rec, dec, g, pi, q, B);
-}
-
-bool intra_timing() {
-  static const bool on = [] {
-    const char* e = std::getenv("TV_DIAG_INTRA");
-    return e && *e == '1';
-  }();
-  return on;
-}
-
-void intra_timing_report() {
-  if (!intra_timing()) return;
-  unsigned long long h[3][8];
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_intra_phase), sizeof(h)) != hipSuccess) return;
-  const char* names[6] = {"staging", "refs", "substitution", "pred+resid", "tb coding", "join"};
-  for (int c = 0; c < 3; ++c) {
-    std::fprintf(stderr, "[TV_DIAG_INTRA] wave %d:", c);
-    for (int k = 0; k < 6; ++k) std::fprintf(stderr, " %s %.1fM", names[k], h[c][k] / 1e6);
-    std::fprintf(stderr, "\n");
-  }
 }
 
 }  // namespace gpu
