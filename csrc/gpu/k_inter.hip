@@ -1,19 +1,20 @@
 // k_inter.hip — P-frame kernels.
 //
-//  k_inter_me     pass A per CTB (320 threads = 5 waves):
-//                   * the source CTB and a 72x72 reference window are staged in LDS as
-//                     32-bit words;
-//                   * integer full search over [-R, R]^2: each thread owns 4 horizontally
-//                     adjacent candidates, loads 3 window words per row and derives the 4
-//                     shifted rows with v_alignbyte, accumulating 16 8x8 SADs per candidate
-//                     with v_sad_u8 (4 pixels / instruction); 16x16 and 32x32 costs are sums
-//                     of 8x8 SADs (SAD reuse);
+//  k_inter_me     pass A per CTB (256 threads = 4 waves):
+//                   * the source CTB and one 38-row window per candidate centre (up to 7)
+//                     are staged in LDS as 32-bit words;
+//                   * integer search of an 8 x 7 window around every centre: each thread owns
+//                     4 horizontally adjacent positions of one 16x16 quadrant, loads 3 window
+//                     words per row and derives the 4 shifted rows with v_alignbyte,
+//                     accumulating its 4 8x8 SADs with v_sad_u8 (4 pixels / instruction);
+//                     16x16 and 32x32 costs are sums of 8x8 SADs (SAD reuse);
 //                   * half- then quarter-pel refinement of all 21 blocks at once, reading
 //                     the precomputed phase planes (no per-block barriers);
 //                   * bottom-up CU split decision.
 //  k_inter_recon  pass B per CTB: luma prediction = phase-plane loads, chroma 4-tap MC,
 //                 residual, MFMA transform/quant, exact inverse, reconstruction.
 #include <stdexcept>
+#include <type_traits>
 
 #include "gpu_common.h"
 #include "k_encode.h"
@@ -32,13 +33,15 @@ namespace gpu {
 //                one v_sad_u8 against zero per source row word.
 //  k_coarse_me   one wave per CTB: the 8x8 quarter-res block vs the previous quarter-res
 //                SOURCE frame, full search over [-Rq, Rq]^2 (Rq = range/4) from an LDS
-//                window, 4 horizontally adjacent candidates per lane via v_alignbyte +
-//                v_sad_u8.  No recon dependency: the coarse field is a lookahead.
-//  k_inter_me    two waves per CTB: up to 7 candidate centres (zero, coarse, 4 coarse
+//                window, 4 horizontally adjacent candidates per lane via v_qsad_pk_u16_u8
+//                (qsad_row).  No recon dependency: the coarse field is a lookahead.
+//  k_inter_me    four waves per CTB: up to 7 candidate centres (zero, coarse, 4 coarse
 //                neighbours, temporal), an [-4,+3] x [-3,+3] integer window each staged in
 //                LDS pre-aligned to the window origin; every lane owns 4 adjacent positions
-//                of one (candidate, row) and accumulates all 16 8x8 SADs (16x16 / 32x32 are
-//                sums: SAD reuse); then half/quarter-pel refinement of the 21 blocks from
+//                of one (candidate, row, 16x16 quadrant) and accumulates its 4 8x8 SADs with
+//                v_alignbyte + v_sad_u8 (16x16 / 32x32 are sums: SAD reuse; the 32x32 sum
+//                crosses the quad's lanes by DPP; v_qsad_pk_u16_u8 measured no faster here:
+//                profiles/README.md); then half/quarter-pel refinement of the 21 blocks from
 //                the phase planes and the bottom-up CU split decision.  Rate = MVD bits
 //                against the CTB predictor.
 // ---------------------------------------------------------------------------------------
@@ -132,6 +135,24 @@ __device__ __forceinline__ uint32_t load4_clamped(const uint8_t* row, int x, int
   return v;
 }
 
+// The sliding SAD step of the coarse search: an 8-pixel source row (s0, s1) against the 4
+// horizontally adjacent positions starting at byte 0 of the window words wp[0..2].
+// v_qsad_pk_u16_u8 adds SAD(bytes i..i+3 of a 64-bit operand, the 4 bytes of a dword) to the
+// 16-bit lane i = 0..3 of a packed accumulator, so {wp[1]:wp[0]} against s0 and {wp[2]:wp[1]}
+// against s1 are the whole row (v_alignbyte + v_sad_u8 take 14 instructions).  The two
+// overlapping 8-byte LDS reads (4-byte aligned: ds_read2_b32) deliver the register pairs.
+// An 8x8 block is at most 64 pixels x 255 = 16320 per lane: exact in 16 bits.
+__device__ __forceinline__ uint64_t lds_pair(const uint32_t* p) {
+  uint64_t v;
+  __builtin_memcpy(&v, p, 8);
+  return v;
+}
+__device__ __forceinline__ uint64_t qsad_row(const uint32_t* wp, uint32_t s0, uint32_t s1, uint64_t acc) {
+  acc = __builtin_amdgcn_qsad_pk_u16_u8(lds_pair(wp), s0, acc);
+  return __builtin_amdgcn_qsad_pk_u16_u8(lds_pair(wp + 1), s1, acc);
+}
+__device__ __forceinline__ unsigned qsad_lane(uint64_t acc, int i) { return (unsigned)(acc >> (16 * i)) & 0xffffu; }
+
 __global__ void __launch_bounds__(256) k_quarter(FrameSet src, uint8_t* q, Geo g) {
   const int b = blockIdx.y, qw = g.W >> 2, qh = g.H >> 2;
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -180,25 +201,14 @@ __global__ void __launch_bounds__(64) k_coarse_me(const uint8_t* qcur, const uin
   int gi = lane / side, dyi = lane - gi * side;
   for (int item = lane; item < groups * side; item += 64) {
     const int dy = dyi - rq, dx0 = 4 * gi - rq;
-    unsigned acc[4] = {0, 0, 0, 0};
+    uint64_t acc = 0;  // 4 positions x u16
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t s0 = sv[2 * j], s1 = sv[2 * j + 1];
-      const int wr = (dyi + j) * pitch + gi;
-      const uint32_t w0 = win[wr], w1 = win[wr + 1], w2 = win[wr + 2];
-      acc[0] = __builtin_amdgcn_sad_u8(w1, s1, __builtin_amdgcn_sad_u8(w0, s0, acc[0]));
-#pragma unroll
-      for (int sft = 1; sft < 4; ++sft) {
-        const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sft);
-        const uint32_t hi = __builtin_amdgcn_alignbyte(w2, w1, sft);
-        acc[sft] = __builtin_amdgcn_sad_u8(hi, s1, __builtin_amdgcn_sad_u8(lo, s0, acc[sft]));
-      }
-    }
+    for (int j = 0; j < 8; ++j) acc = qsad_row(win + (dyi + j) * pitch + gi, sv[2 * j], sv[2 * j + 1], acc);
 #pragma unroll
     for (int sft = 0; sft < 4; ++sft) {
       const int dx = dx0 + sft;
       if (dx > rq) continue;
-      const unsigned v = ((acc[sft] + (unsigned)me_coarse_pen(penL, dx, dy)) << 13) | (unsigned)(dyi * side + dx + rq);
+      const unsigned v = ((qsad_lane(acc, sft) + (unsigned)me_coarse_pen(penL, dx, dy)) << 13) | (unsigned)(dyi * side + dx + rq);
       best = v < best ? v : best;
     }
     gi += step_g;
@@ -419,33 +429,160 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   // ------------------------ half- then quarter-pel refinement ---------------------------
   const uint8_t* sb = reinterpret_cast<const uint8_t*>(s32);
   const uint8_t* ph = phase + (long)b * 16 * g.psz;
-#pragma unroll 1  // two passes of one loop body: unrolled, the kernel grows by a third and runs slower
-  for (int step = 2; step >= 1; step >>= 1) {
-    __syncthreads();  // bmv of the previous step / the integer search
-    // A thread owns a group of 8 rows x 8 pixels of one (block, candidate): per row it
-    // loads 3 aligned dwords of the phase plane, forms the 2 shifted dwords with v_alignbyte
-    // and accumulates with v_sad_u8.  16 (8x8) + 16 (16x16) + 16 (32x32) groups per candidate,
-    // 384 in all = 1.5 per thread (half the threads run a second pass while the others wait
-    // at the barrier).
-    constexpr int ROWS = 8, N8 = 16, NC = 3 * N8;  // rows per group, groups per class / candidate
+  // A group is 8 rows x 8 pixels of one block: 16 (8x8) + 16 (16x16) + 16 (32x32) groups.
+  constexpr int ROWS = 8, N8 = 16, NC = 3 * N8;  // rows per group, groups per class / candidate
+  auto grp_geom = [](int r, int& bi, int& row0, int& col0) {
+    if (r < N8) {
+      bi = r;
+      row0 = 0;
+      col0 = 0;
+    } else if (r < 2 * N8) {
+      const int q = (r - N8) % 4;
+      bi = 16 + (r - N8) / 4;
+      row0 = ROWS * (q >> 1);
+      col0 = 8 * (q & 1);
+    } else {
+      const int q = r - 2 * N8;
+      bi = 20;
+      row0 = ROWS * (q >> 2);
+      col0 = 8 * (q & 3);
+    }
+  };
+  // the sub-pel argmin of the 21 blocks over the 8 neighbours at distance `step` (quarter pels)
+  auto subpel_argmin = [&](int step) {
+    if (tid < 21) {
+      unsigned bestv = (unsigned)bcost[tid] << 4;
+      for (int k = 0; k < 8; ++k) {
+        int ox, oy;
+        me_cand_offset(k, ox, oy);
+        const int mx = bmv[tid][0] + ox * step, my = bmv[tid][1] + oy * step;
+        const unsigned v =
+            ((unsigned)(subsad[tid][k] + penmv[me_pen_index(mx - pmv[0], my - pmv[1])]) << 4) | (unsigned)(k + 1);
+        bestv = v < bestv ? v : bestv;
+      }
+      const int kk = (int)(bestv & 15);
+      bcost[tid] = (int)(bestv >> 4);
+      if (kk) {
+        int ox, oy;
+        me_cand_offset(kk - 1, ox, oy);
+        bmv[tid][0] += ox * step;
+        bmv[tid][1] += oy * step;
+      }
+    }
+  };
+  __syncthreads();  // bmv of the integer search
+  {
+    // Half-pel round.  bmv is at integer pels, so the 8 neighbours lie on three phase planes
+    // only: (+-2, 0) on plane fx = 2 at integer x - 1 and x, (0, +-2) on fy = 2 at rows y - 1
+    // and y, the four diagonals on (2, 2) at both.  A wave takes one plane set, a lane one
+    // group of it: it loads the set's patch once (8 or 9 rows of 3 aligned dwords, which
+    // hold the 9 bytes from x - 1 at any alignment) and takes its 2 / 2 / 4 SADs from it --
+    // 26 row loads per group instead of 64, in one pass.  sad[2 * lower + right].
+    const int set = __builtin_amdgcn_readfirstlane(tid >> 6), r = tid & 63;  // H, V, HV
+    if (set < 3 && r < NC) {
+      const bool two_x = set != 1, two_y = set != 0;
+      int bi, row0, col0;
+      grp_geom(r, bi, row0, col0);
+      int bx, by, l2b;
+      me_blk_geom(bi, bx, by, l2b);
+      const uint8_t* P = ph + (long)((two_x ? 2 : 0) + 4 * (two_y ? 2 : 0)) * g.psz;
+      // patch origin = the position of the upper left candidate
+      const int gx0 = cx + bx + col0 + (bmv[bi][0] >> 2) - (two_x ? 1 : 0);
+      const int gy0 = cy + by + row0 + (bmv[bi][1] >> 2) - (two_y ? 1 : 0);
+      const int sr0 = by + row0, sw0 = (bx + col0) >> 2;  // source row / word of row 0
+      unsigned sad[4] = {0, 0, 0, 0};
+      // straight-line per plane set (the flags are compile-time), so a lane's row loads are
+      // all in flight together
+      auto patch_sads = [&](auto TX, auto TY) {
+        constexpr bool kTwoX = decltype(TX)::value, kTwoY = decltype(TY)::value;
+        const int a = gx0 & ~3, sh = gx0 & 3;
+        const uint8_t* rowp = P + (long)(gy0 + 8) * g.pw16 + a + 8;
+        uint32_t p0 = 0, p1 = 0;  // the source row above
+#pragma unroll
+        for (int j = 0; j < ROWS + (kTwoY ? 1 : 0); ++j) {
+          const uint32_t* wp = reinterpret_cast<const uint32_t*>(rowp + (long)j * g.pw16);
+          const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
+          const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh);
+          const uint32_t hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
+          uint32_t lo1 = 0, hi1 = 0;  // one pixel to the right
+          if (kTwoX) {
+            lo1 = __builtin_amdgcn_alignbyte(hi, lo, 1);
+            hi1 = __builtin_amdgcn_alignbyte(w2 >> (8 * sh), hi, 1);
+          }
+          uint32_t c0 = 0, c1 = 0;
+          if (j < ROWS) {
+            const int sw = src_word(sr0 + j, sw0);
+            c0 = s32[sw];
+            c1 = s32[sw + 1];
+            sad[0] = __builtin_amdgcn_sad_u8(hi, c1, __builtin_amdgcn_sad_u8(lo, c0, sad[0]));
+            if (kTwoX) sad[1] = __builtin_amdgcn_sad_u8(hi1, c1, __builtin_amdgcn_sad_u8(lo1, c0, sad[1]));
+          }
+          if (kTwoY && j > 0) {
+            sad[2] = __builtin_amdgcn_sad_u8(hi, p1, __builtin_amdgcn_sad_u8(lo, p0, sad[2]));
+            if (kTwoX) sad[3] = __builtin_amdgcn_sad_u8(hi1, p1, __builtin_amdgcn_sad_u8(lo1, p0, sad[3]));
+          }
+          p0 = c0;
+          p1 = c1;
+        }
+      };
+      if (gx0 >= -8 && gx0 + 11 <= g.W + 7 && gy0 >= -8 && gy0 + ROWS - 1 + (two_y ? 1 : 0) <= g.H + 7) {
+        if (set == 0) {
+          patch_sads(std::true_type{}, std::false_type{});
+        } else if (set == 1) {
+          patch_sads(std::false_type{}, std::true_type{});
+        } else {
+          patch_sads(std::true_type{}, std::true_type{});
+        }
+      } else {  // the patch touches the clamped border: per candidate, per pixel
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+          if (((c & 1) && !two_x) || ((c >> 1) && !two_y)) continue;
+          unsigned t = 0;
+          for (int j = 0; j < ROWS; ++j) {
+            const int gy = clip3(-8, g.H + 7, gy0 + (c >> 1) + j);
+            for (int i = 0; i < 8; ++i) {
+              const int gx = clip3(-8, g.W + 7, gx0 + (c & 1) + i);
+              t += tv_abs((int)sb[4 * src_word(sr0 + j, 0) + bx + col0 + i] - (int)P[(long)(gy + 8) * g.pw16 + gx + 8]);
+            }
+          }
+          sad[c] = t;
+        }
+      }
+      // group sums as in the quarter-pel round below; neighbour k of offset (ox, oy) is its
+      // raster index in the 3 x 3 neighbourhood without the centre (me_cand_offset)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (((c & 1) && !two_x) || ((c >> 1) && !two_y)) continue;
+        const int ox = two_x ? 2 * (c & 1) - 1 : 0, oy = two_y ? 2 * (c >> 1) - 1 : 0;
+        const int idx = 3 * (oy + 1) + ox + 1, k = idx < 4 ? idx : idx - 1;
+        const int s1 = (int)sad[c];
+        int s4 = s1 + dpp::mov<dpp::kQuadXor1>(s1);
+        s4 += dpp::mov<dpp::kQuadXor2>(s4);
+        int s16 = s4 + dpp::mov<dpp::kRowHalfMirror>(s4);
+        s16 += dpp::mov<dpp::kRowMirror>(s16);
+        if (r < N8) {
+          subsad[bi][k] = s1;
+        } else if (r < 2 * N8) {
+          if ((r - N8) % 4 == 0) subsad[bi][k] = s4;
+        } else if (r == 2 * N8) {
+          subsad[bi][k] = s16;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  subpel_argmin(2);
+  __syncthreads();  // bmv of the half-pel round
+  // Quarter-pel round: the 8 neighbours lie on 8 different planes.  A thread owns one group
+  // of one (block, candidate): per row it loads 3 aligned dwords of the phase plane, forms
+  // the 2 shifted dwords with v_alignbyte and accumulates with v_sad_u8.  384 groups = 1.5
+  // per thread (half the threads run a second pass while the others wait at the barrier).
+  {
+    constexpr int step = 1;
     for (int grp = tid; grp < 8 * NC; grp += kMeThreads) {
       const int k = grp / NC, r = grp - k * NC;
       int bi, row0, col0;
-      if (r < N8) {
-        bi = r;
-        row0 = 0;
-        col0 = 0;
-      } else if (r < 2 * N8) {
-        const int q = (r - N8) % 4;
-        bi = 16 + (r - N8) / 4;
-        row0 = ROWS * (q >> 1);
-        col0 = 8 * (q & 1);
-      } else {
-        const int q = r - 2 * N8;
-        bi = 20;
-        row0 = ROWS * (q >> 2);
-        col0 = 8 * (q & 3);
-      }
+      grp_geom(r, bi, row0, col0);
       int bx, by, l2b;
       me_blk_geom(bi, bx, by, l2b);
       int ox, oy;
@@ -493,28 +630,10 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
         subsad[bi][k] = s16;
       }
     }
-    __syncthreads();
-    if (tid < 21) {
-      unsigned bestv = (unsigned)bcost[tid] << 4;
-      for (int k = 0; k < 8; ++k) {
-        int ox, oy;
-        me_cand_offset(k, ox, oy);
-        const int mx = bmv[tid][0] + ox * step, my = bmv[tid][1] + oy * step;
-        const unsigned v =
-            ((unsigned)(subsad[tid][k] + penmv[me_pen_index(mx - pmv[0], my - pmv[1])]) << 4) | (unsigned)(k + 1);
-        bestv = v < bestv ? v : bestv;
-      }
-      const int kk = (int)(bestv & 15);
-      bcost[tid] = (int)(bestv >> 4);
-      if (kk) {
-        int ox, oy;
-        me_cand_offset(kk - 1, ox, oy);
-        bmv[tid][0] += ox * step;
-        bmv[tid][1] += oy * step;
-      }
-    }
-    __syncthreads();
   }
+  __syncthreads();
+  subpel_argmin(1);
+  __syncthreads();
 
   // B picture: hand this list's 21 block results to k_bi_decide
   if (bout) {
