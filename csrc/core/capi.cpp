@@ -5,9 +5,11 @@
 #include <string>
 #include <vector>
 
+#include "tv/av1_enc.h"
 #include "tv/container.h"
 #include "tv/cpu_encoder.h"
 #include "tv/hevc_codec.h"
+#include "tv/me_model.h"
 #include "tv/synth.h"
 
 using namespace tv;
@@ -300,6 +302,19 @@ int tv_mux_file(const uint8_t* const* segs, const size_t* sizes, int nseg, int w
   });
 }
 size_t tv_side_track_size() { return sizeof(SideTrack); }
+
+// ------------------------------------ cost model (tests) --------------------------------
+// the MV-rate model evaluated over arrays: est[i] = mv_bits_est, idx[i] = me_pen_index of
+// (dx[i], dy[i]); bits[i] = av1::mv_comp_bits(d[i])
+void tv_mv_rate(const int* dx, const int* dy, int n, int* est, int* idx) {
+  for (int i = 0; i < n; ++i) {
+    est[i] = mv_bits_est(dx[i], dy[i]);
+    idx[i] = me_pen_index(dx[i], dy[i]);
+  }
+}
+void tv_av1_mv_comp_bits(const int* d, int n, int* bits) {
+  for (int i = 0; i < n; ++i) bits[i] = av1::mv_comp_bits(d[i]);
+}
 int tv_demux_mp4(const uint8_t* mp4, size_t n, int* w, int* h, int* nframes, int* timescale,
                  int* delta, void* out) {
   return guard([&] { static_cast<Bytes*>(out)->v = demux_mp4(mp4, n, w, h, nframes, timescale, delta); });

@@ -181,9 +181,10 @@ __global__ void __launch_bounds__(64) k_coarse_me(const uint8_t* qcur, const uin
   const uint8_t* P = qprev + (long)b * qw * qh;
   __shared__ uint32_t s32[16];
   extern __shared__ uint32_t win[];  // (8 + 2 rq) rows x ((rq / 2 + 3) | 1) words: sized per launch
-  __shared__ int penL[64];  // the MV-rate table: read per candidate (a global load chain before)
+  // the coarse MV-rate table (me_coarse_pen's scaling applied once): read per candidate
+  __shared__ int penL[64];
   const int side = 2 * rq + 1, rows = 8 + 2 * rq, wpr = rq / 2 + 3, pitch = wpr | 1;
-  penL[lane] = pen.mv[lane];
+  penL[lane] = (pen.mv[lane] + 8) >> 4;
   if (lane < 16) s32[lane] = *reinterpret_cast<const uint32_t*>(C + (long)(y0 + (lane >> 1)) * qw + x0 + 4 * (lane & 1));
   for (int w = lane; w < rows * wpr; w += 64) {
     const int r = w / wpr, c = w - r * wpr;
@@ -201,15 +202,16 @@ __global__ void __launch_bounds__(64) k_coarse_me(const uint8_t* qcur, const uin
   int gi = lane / side, dyi = lane - gi * side;
   for (int item = lane; item < groups * side; item += 64) {
     const int dy = dyi - rq, dx0 = 4 * gi - rq;
+    const int leny = mv_bits_len(16 * dy);  // one dy per item: the 4 positions add their dx length
     uint64_t acc = 0;  // 4 positions x u16
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc = qsad_row(win + (dyi + j) * pitch + gi, sv[2 * j], sv[2 * j + 1], acc);
 #pragma unroll
-    for (int sft = 0; sft < 4; ++sft) {
+    for (int sft = 0; sft < 4; ++sft) {  // no branch: the 4 table reads are in flight together
       const int dx = dx0 + sft;
-      if (dx > rq) continue;
-      const unsigned v = ((qsad_lane(acc, sft) + (unsigned)me_coarse_pen(penL, dx, dy)) << 13) | (unsigned)(dyi * side + dx + rq);
-      best = v < best ? v : best;
+      const unsigned rate = (unsigned)penL[me_pen_index_len(mv_bits_len(16 * dx), leny)];  // == me_coarse_pen
+      const unsigned v = ((qsad_lane(acc, sft) + rate) << 13) | (unsigned)(dyi * side + dx + rq);
+      best = (dx <= rq && v < best) ? v : best;  // the last group's positions past +rq do not count
     }
     gi += step_g;
     dyi += step_d;
@@ -237,7 +239,9 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   const int tid = threadIdx.x;
   int ctu, b;
   xcd_ctb(ctu, b);
-  const Penalties& pen = rc->pen[dec.qp[b]];
+  // the picture's QP is one value per workgroup: kept scalar, so the table's address does not
+  // hold a VGPR pair down to the split decision at the end
+  const Penalties& pen = rc->pen[__builtin_amdgcn_readfirstlane((int)dec.qp[b])];
   __shared__ int penmv[64];  // visible after the first barrier below
   if (tid < 64) penmv[tid] = pen.mv[tid];
   const int cxi = ctu % g.wc, cyi = ctu / g.wc, cx = cxi * 32, cy = cyi * 32;
@@ -344,10 +348,11 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
     const int pos0 = k * kMePosPerCand + dyi * kMeWinW + 4 * gs;
     const int my = cand[k][1] + kMeWinY0 + dyi;
     unsigned mvc[4];
+    const int leny = mv_bits_len(4 * my - pmv[1]);  // one my per item, four mx
 #pragma unroll
     for (int sft = 0; sft < 4; ++sft) {
       const int mx = cand[k][0] + kMeWinX0 + 4 * gs + sft;
-      mvc[sft] = (unsigned)penmv[me_pen_index(4 * mx - pmv[0], 4 * my - pmv[1])];
+      mvc[sft] = (unsigned)penmv[me_pen_index_len(mv_bits_len(4 * mx - pmv[0]), leny)];
     }
     const int qx = (qd & 1) * 16, qy = (qd >> 1) * 16;
 
@@ -573,61 +578,101 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   __syncthreads();
   subpel_argmin(2);
   __syncthreads();  // bmv of the half-pel round
-  // Quarter-pel round: the 8 neighbours lie on 8 different planes.  A thread owns one group
-  // of one (block, candidate): per row it loads 3 aligned dwords of the phase plane, forms
-  // the 2 shifted dwords with v_alignbyte and accumulates with v_sad_u8.  384 groups = 1.5
-  // per thread (half the threads run a second pass while the others wait at the barrier).
+  // Quarter-pel round: the 8 neighbours lie on 8 different planes.  One wave per block class
+  // (8x8, 16x16, 32x32 groups; the fourth wave goes straight to the barrier), a lane = one
+  // group and one candidate pair (k = 2p, 2p + 1): it decodes its geometry and reads its 8
+  // source rows once, then takes both candidates' SADs (per row 3 aligned dwords of the phase
+  // plane, v_alignbyte, v_sad_u8) -- all 384 (group, candidate) cells in one pass.  A DPP row
+  // is one pair's 16 groups, so the quad / row sums below are one block's.
   {
     constexpr int step = 1;
-    for (int grp = tid; grp < 8 * NC; grp += kMeThreads) {
-      const int k = grp / NC, r = grp - k * NC;
+    const int cls = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
+    if (cls < 3) {
+      const int r = cls * N8 + (ln & 15), k0 = 2 * (ln >> 4);
       int bi, row0, col0;
       grp_geom(r, bi, row0, col0);
       int bx, by, l2b;
       me_blk_geom(bi, bx, by, l2b);
-      int ox, oy;
-      me_cand_offset(k, ox, oy);
-      const int mx = bmv[bi][0] + ox * step, my = bmv[bi][1] + oy * step;
-      const uint8_t* P = ph + (long)((mx & 3) + 4 * (my & 3)) * g.psz;
-      const int gx0 = cx + bx + col0 + (mx >> 2);
-      const int gy0 = cy + by + row0 + (my >> 2);
       const int sr0 = by + row0, sw0 = (bx + col0) >> 2;  // source row / word of row 0
-      unsigned sad = 0;
-      if (gx0 >= -8 && gx0 + 11 <= g.W + 7 && gy0 >= -8 && gy0 + ROWS - 1 <= g.H + 7) {
-        const int a = gx0 & ~3, sh = gx0 & 3;
-        const uint8_t* rowp = P + (long)(gy0 + 8) * g.pw16 + a + 8;
+      int oxa, oya, oxb, oyb;
+      me_cand_offset(k0, oxa, oya);
+      me_cand_offset(k0 + 1, oxb, oyb);
+      const int mxa = bmv[bi][0] + oxa * step, mya = bmv[bi][1] + oya * step;
+      const int mxb = bmv[bi][0] + oxb * step, myb = bmv[bi][1] + oyb * step;
+      const uint8_t* Pa = ph + (long)((mxa & 3) + 4 * (mya & 3)) * g.psz;
+      const uint8_t* Pb = ph + (long)((mxb & 3) + 4 * (myb & 3)) * g.psz;
+      const int gxa = cx + bx + col0 + (mxa >> 2), gya = cy + by + row0 + (mya >> 2);
+      const int gxb = cx + bx + col0 + (mxb >> 2), gyb = cy + by + row0 + (myb >> 2);
+      auto inside = [&](int gx0, int gy0) { return gx0 >= -8 && gx0 + 11 <= g.W + 7 && gy0 >= -8 && gy0 + ROWS - 1 <= g.H + 7; };
+      unsigned sada = 0, sadb = 0;
+      if (inside(gxa, gya) && inside(gxb, gyb)) {
+        const uint8_t* rpa = Pa + (long)(gya + 8) * g.pw16 + (gxa & ~3) + 8;
+        const uint8_t* rpb = Pb + (long)(gyb + 8) * g.pw16 + (gxb & ~3) + 8;
+        const int sha = gxa & 3, shb = gxb & 3;
+        // 4 rows of both candidates (24 dwords) in flight at a time: all 48 do not fit 64 VGPRs
+#pragma unroll 1
+        for (int h = 0; h < ROWS; h += ROWS / 2) {
 #pragma unroll
-        for (int j = 0; j < ROWS; ++j) {
-          const uint32_t* wp = reinterpret_cast<const uint32_t*>(rowp + (long)j * g.pw16);
-          const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
-          const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh);
-          const uint32_t hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
-          const int sw = src_word(sr0 + j, sw0);
-          sad = __builtin_amdgcn_sad_u8(hi, s32[sw + 1], __builtin_amdgcn_sad_u8(lo, s32[sw], sad));
-        }
-      } else {  // touches the clamped border: per-pixel path
-        for (int j = 0; j < ROWS; ++j) {
-          const int gy = clip3(-8, g.H + 7, gy0 + j);
-          for (int i = 0; i < 8; ++i) {
-            const int gx = clip3(-8, g.W + 7, gx0 + i);
-            sad += tv_abs((int)sb[4 * src_word(sr0 + j, 0) + bx + col0 + i] - (int)P[(long)(gy + 8) * g.pw16 + gx + 8]);
+          for (int jj = 0; jj < ROWS / 2; ++jj) {
+            const int j = h + jj;
+            const uint32_t* wa = reinterpret_cast<const uint32_t*>(rpa + (long)j * g.pw16);
+            const uint32_t* wb = reinterpret_cast<const uint32_t*>(rpb + (long)j * g.pw16);
+            const uint32_t a0 = wa[0], a1 = wa[1], a2 = wa[2], b0 = wb[0], b1 = wb[1], b2 = wb[2];
+            const int sw = src_word(sr0 + j, sw0);
+            const uint32_t c0 = s32[sw], c1 = s32[sw + 1];
+            sada = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(a2, a1, sha), c1,
+                                           __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(a1, a0, sha), c0, sada));
+            sadb = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(b2, b1, shb), c1,
+                                           __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(b1, b0, shb), c0, sadb));
           }
         }
+      } else {  // a candidate touches the clamped border: one at a time, per pixel where it does
+#pragma unroll 1
+        for (int c = 0; c < 2; ++c) {
+          const uint8_t* P = c ? Pb : Pa;
+          const int gx0 = c ? gxb : gxa, gy0 = c ? gyb : gya;
+          unsigned sad = 0;
+          if (inside(gx0, gy0)) {
+            const int a = gx0 & ~3, sh = gx0 & 3;
+            const uint8_t* rowp = P + (long)(gy0 + 8) * g.pw16 + a + 8;
+#pragma unroll
+            for (int j = 0; j < ROWS; ++j) {
+              const uint32_t* wp = reinterpret_cast<const uint32_t*>(rowp + (long)j * g.pw16);
+              const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
+              const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, sh);
+              const uint32_t hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
+              const int sw = src_word(sr0 + j, sw0);
+              sad = __builtin_amdgcn_sad_u8(hi, s32[sw + 1], __builtin_amdgcn_sad_u8(lo, s32[sw], sad));
+            }
+          } else {
+            for (int j = 0; j < ROWS; ++j) {
+              const int gy = clip3(-8, g.H + 7, gy0 + j);
+              for (int i = 0; i < 8; ++i) {
+                const int gx = clip3(-8, g.W + 7, gx0 + i);
+                sad += tv_abs((int)sb[4 * src_word(sr0 + j, 0) + bx + col0 + i] - (int)P[(long)(gy + 8) * g.pw16 + gx + 8]);
+              }
+            }
+          }
+          if (c) sadb = sad; else sada = sad;
+        }
       }
-      // group sums on the VALU (a wave's lanes all run the same passes): a lane = an 8x8
-      // block, an aligned group of 4 lanes = a 16x16 block, of 16 = the 32x32 block -- every
-      // (block, candidate) cell is written exactly once, by a plain store
-      const int s1 = (int)sad;
-      int s4 = s1 + dpp::mov<dpp::kQuadXor1>(s1);
-      s4 += dpp::mov<dpp::kQuadXor2>(s4);
-      int s16 = s4 + dpp::mov<dpp::kRowHalfMirror>(s4);
-      s16 += dpp::mov<dpp::kRowMirror>(s16);
-      if (r < N8) {
-        subsad[bi][k] = s1;
-      } else if (r < 2 * N8) {
-        if ((r - N8) % 4 == 0) subsad[bi][k] = s4;
-      } else if (r == 2 * N8) {
-        subsad[bi][k] = s16;
+      // group sums on the VALU (all 64 lanes of the wave are here): a lane = an 8x8 block, an
+      // aligned group of 4 lanes = a 16x16 block, of 16 = the 32x32 block -- every (block,
+      // candidate) cell is written exactly once, by a plain store
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int s1 = (int)(c ? sadb : sada), k = k0 + c;
+        int s4 = s1 + dpp::mov<dpp::kQuadXor1>(s1);
+        s4 += dpp::mov<dpp::kQuadXor2>(s4);
+        int s16 = s4 + dpp::mov<dpp::kRowHalfMirror>(s4);
+        s16 += dpp::mov<dpp::kRowMirror>(s16);
+        if (cls == 0) {
+          subsad[bi][k] = s1;
+        } else if (cls == 1) {
+          if ((ln & 3) == 0) subsad[bi][k] = s4;
+        } else if ((ln & 15) == 0) {
+          subsad[bi][k] = s16;
+        }
       }
     }
   }

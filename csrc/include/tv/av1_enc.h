@@ -267,14 +267,8 @@ TV_HD int satd4(const int* d) {
 }
 // approximate bits of one MV component difference (1/8 units, even)
 TV_HD int mv_comp_bits(int d) {
-  int a = (d < 0 ? -d : d) >> 1;  // quarter-pel units
-  if (!a) return 1;
-  int b = 0;
-  while (a) {
-    ++b;
-    a >>= 1;
-  }
-  return 2 * b + 2;
+  const int a = tv_abs(d) >> 1;  // quarter-pel units
+  return a ? 2 * tv_bitlen((unsigned)a) + 2 : 1;
 }
 // approximate mode bits of the key-frame intra candidates (x16)
 TV_HD int intra_mode_bits16(int m) {
@@ -307,14 +301,7 @@ constexpr uint64_t kCdefMaskUV = cdef_mask(kCdefPriUV, 4, kCdefSec, 2);
 constexpr int kNumLrSets = 2;
 TV_HD int lr_set(int i) { return i == 0 ? 4 : 10; }
 constexpr int kXqdMin0 = -96, kXqdMax0 = 31, kXqdMin1 = -32, kXqdMax1 = 95, kXqdMid0 = -32, kXqdMid1 = 31;
-TV_HD int bitlen64(unsigned long long v) {
-  int n = 0;
-  while (v) {
-    ++n;
-    v >>= 1;
-  }
-  return n;
-}
+TV_HD int bitlen64(unsigned long long v) { return tv_bitlen64(v); }
 TV_HD long long div_round(long long n, long long d) { return n >= 0 ? (n + d / 2) / d : -((-n + d / 2) / d); }
 // Coded weights (xqd0, xqd1) of a unit from its sgr_stats (H00 H01 H11 c0 c1: normal
 // equations of the weights a, b of F0 - u and F1 - u, 1/128 units).  The decoder applies

@@ -508,24 +508,16 @@ TV_HD bool rqt_split(const int* sad4, int npx = 256) {  // npx: samples per quad
   return 2 * lo < hi && lo < npx * kRqtClean;
 }
 
-// Rough bin count of an mvd pair (encoder cost model; CPU and GPU use the same).
-TV_HD int mv_bits_est(int dx, int dy) {
-  int bits = 0;
-  for (int c = 0; c < 2; ++c) {
-    int a = tv_abs(c ? dy : dx);
-    if (a == 0) {
-      bits += 1;
-      continue;
-    }
-    int v = a + 1, n = 0;
-    while (v > 1) {
-      v >>= 1;
-      ++n;
-    }
-    bits += 2 * n + 1;
-  }
-  return bits;
-}
+// Bit length of v: the position of its highest set bit, counted from 1 (0 for v == 0).  One
+// count-leading-zeros on the device (v_ffbh_u32), never a per-bit loop: the motion search
+// calls it per candidate.
+TV_HD int tv_bitlen(unsigned v) { return v ? 32 - __builtin_clz(v) : 0; }
+TV_HD int tv_bitlen64(unsigned long long v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+// Rough bin count of an mvd pair (encoder cost model; CPU and GPU use the same): per
+// component 2 * floor(log2(|d| + 1)) + 1, an Exp-Golomb-like length (1 for d == 0).
+TV_HD int mv_bits_len(int d) { return 2 * tv_bitlen((unsigned)tv_abs(d) + 1u) - 1; }
+TV_HD int mv_bits_est(int dx, int dy) { return mv_bits_len(dx) + mv_bits_len(dy); }
 
 // ------------------------------------ scan orders ---------------------------------------
 // 4x4 up-right diagonal scan: position i -> (x, y) packed as x | y<<2

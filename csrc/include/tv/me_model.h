@@ -27,6 +27,9 @@ constexpr int kMeWinH = kMeWinY1 - kMeWinY0 + 1;  // 7
 constexpr int kMePosPerCand = kMeWinW * kMeWinH;  // 56
 
 TV_HD int me_pen_index(int dx, int dy) { return tv_min(63, mv_bits_est(dx, dy)); }
+// the same from per-component lengths (mv_bits_len): a search that walks one axis keeps the
+// other axis' length
+TV_HD int me_pen_index_len(int lenx, int leny) { return tv_min(63, lenx + leny); }
 
 // coarse rate term for a quarter-res displacement (dxq, dyq): the full-res penalty / 16
 // (a quarter-res SAD sums 16x fewer, 16x averaged samples)
