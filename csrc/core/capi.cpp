@@ -11,6 +11,7 @@
 #include "tv/hevc_codec.h"
 #include "tv/me_model.h"
 #include "tv/synth.h"
+#include "tv/tb_frag.h"
 
 using namespace tv;
 
@@ -314,6 +315,26 @@ void tv_mv_rate(const int* dx, const int* dy, int n, int* est, int* idx) {
 }
 void tv_av1_mv_comp_bits(const int* d, int n, int* bits) {
   for (int i = 0; i < n; ++i) bits[i] = av1::mv_comp_bits(d[i]);
+}
+// the f16 fragment tables of the GPU TB path (tv/tb_frag.h) expanded to integer matrices
+// [n][k]: which = 0 / 1 the 32x32 pair into out[1024]; 2 + 2 * s + o the 16x16 composite of
+// TB size 16 >> s, orientation o, into out[256].  Returns the matrix side, 0 for a bad index.
+int tv_tb_frag_expand(int which, int* out) {
+  static constexpr TbFragTables t = make_tb_frag();
+  if (which < 0 || which >= 8) return 0;
+  const int side = which < 2 ? 32 : 16;
+  for (int n = 0; n < side; ++n)
+    for (int k = 0; k < side; ++k)
+      out[n * side + k] = int_of_f16_bits(which < 2 ? t.t32[which][n][k] : t.c16[(which - 2) >> 1][which & 1][n][k]);
+  return side;
+}
+// ref[i] = quant_level(coef[i], qp, log2N, inter), fast[i] = the 32-bit quant_fast of the GPU path
+void tv_quant_levels(const int* coef, int n, int qp, int log2N, int* ref, int* fast) {
+  const QuantParams q = quant_params(qp, log2N);
+  for (int i = 0; i < n; ++i) {
+    ref[i] = quant_level(coef[i], qp, log2N, false);
+    fast[i] = quant_fast(coef[i], q);
+  }
 }
 int tv_demux_mp4(const uint8_t* mp4, size_t n, int* w, int* h, int* nframes, int* timescale,
                  int* delta, void* out) {

@@ -12,7 +12,9 @@
 //                     the precomputed phase planes (no per-block barriers);
 //                   * bottom-up CU split decision.
 //  k_inter_recon  pass B per CTB: luma prediction = phase-plane loads, chroma 4-tap MC,
-//                 residual, MFMA transform/quant, exact inverse, reconstruction.
+//                 residual, MFMA transform/quant, exact inverse, reconstruction; the MFMA
+//                 operands are f16 fragments (constant tables of tv/tb_frag.h, intermediates
+//                 stored split by their producer), the quantiser 32-bit with per-tile parameters.
 #include <stdexcept>
 #include <type_traits>
 
@@ -87,9 +89,12 @@ __device__ __forceinline__ int me_blk8_of(int q, int r) {
   return (((q >> 1) * 2 + (r >> 1)) << 2) + (q & 1) * 2 + (r & 1);
 }
 // tv::dequant_level in 32-bit arithmetic: with m = 16 * levelScale << (qp / 6) and the level
-// clamped to +-thr, where thr * m just exceeds (32768 + 1) << bdShift, a clamped level still
+// clamped to +-thr, where thr * m is at least (32768 + 1) << bdShift, a clamped level still
 // saturates to the same int16 bound and every unclamped product fits in 32 bits -- the same
-// result as the 64-bit golden form, with a med3 + mad + shift + med3 per level.
+// result as the 64-bit golden form, with a med3 + mad + shift + med3 per level.  Any such thr
+// gives the same levels, so it comes without a division: with 2^p <= m < 2^(p+1), thr =
+// (32769 << bdShift >> p) + 1 >= (32769 << bdShift) / m, and thr * m < 2 * (32769 << bdShift)
+// + 2^(p+1) <= 2^25 + 2^19 (bdShift <= 8, m < 2^19).
 struct DeqParams {
   int m, thr, sh, rnd;
 };
@@ -98,7 +103,7 @@ __device__ __forceinline__ DeqParams deq_params(int qp, int log2N) {
   d.sh = 8 + log2N - 5;
   d.rnd = 1 << (d.sh - 1);
   d.m = (16 * level_scale(qp)) << (qp / 6);
-  d.thr = (((32768 + 1) << d.sh) + d.m - 1) / d.m;
+  d.thr = (((32768 + 1) << d.sh) >> (31 - __builtin_clz(d.m))) + 1;
   return d;
 }
 __device__ __forceinline__ int deq_fast(int level, const DeqParams& d) {
@@ -856,12 +861,27 @@ __global__ void __launch_bounds__(256) k_bi_decide(FrameSet src, const uint8_t* 
 // 2 chroma tiles) with no VALU dot products at all.  Every operand is an integer of <= 9
 // bits (8-bit split halves where needed) so every product and partial sum is exact in f32:
 // bit-identical to tv::forward_transform / tv::inverse_transform (see tb_coder.h).
+//
+// Operands are MFMA fragments (tb_coder.h frag_tile*), not per-element gathers.  The DCT side
+// of every product -- T32, its transpose and the block-diagonal composites -- is a constant:
+// tv/tb_frag.h builds it at compile time as f16 in lane order and the workgroup copies the
+// 7 KB into LDS, one 16- / 8-byte read per lane and tile.  The intermediate of each
+// direction (stage 1 -> 2, stage 3 -> 4) is written by its producer already split into f16
+// hi / lo images, row-major, which is the K order of the consuming A operand.  Only the B
+// operands of stages 1 and 3 (residual, dequantised levels: K runs down a column of the
+// row-major int16 planes the entropy path reads) are still converted per element.  A lane's
+// four outputs of a tile are consecutive columns of one row (tb_coder.h frag_tile): one
+// 8-byte store into the f16 images or the level plane, one dword of reconstruction.  TB size,
+// TB id and the quantiser parameters are uniform per tile and computed once per tile; a
+// lane's four levels belong to one TB and update its statistics with one pair of atomics.
 // ---------------------------------------------------------------------------------------
+constexpr int kTmpYP = 40, kTmpCP = 16;  // f16 row pitches (luma padded by 16 bytes: rows stay 16-byte aligned)
+__constant__ TbFragTables kTbFragDev = make_tb_frag();
+
 struct PReconLds {
-  int16_t T[32][34];          // DCT-32 (every smaller DCT is a row subsample); rows padded to
-                              // 17 dwords: column reads across lanes hit distinct banks
-  int tmpY[32 * 33];          // stage 1 / stage 3 outputs (luma)
-  int tmpC[2][16 * 17];       // stage 1 / stage 3 outputs (Cb, Cr), rows of 17 (bank spread)
+  alignas(16) TbFragTables F;  // the constant operands as f16 fragments (tv/tb_frag.h)
+  alignas(16) _Float16 tmpYh[32 * kTmpYP], tmpYl[32 * kTmpYP];        // stage 1 / stage 3 outputs (luma), v = 256 hi + lo
+  alignas(16) _Float16 tmpCh[2][16 * kTmpCP], tmpCl[2][16 * kTmpCP];  // the same for Cb, Cr
   int16_t resY[32 * 32];      // residual, later levels (luma)
   int16_t resC[2][16 * 16];   // residual, later levels (chroma)
   uint8_t predY[32 * 32];
@@ -896,16 +916,13 @@ __device__ __forceinline__ int pr_tb_chroma(const PReconLds& L, int p, int x, in
   const int base = 16 + 16 * p;
   return t == 0 ? base : (t == 1 ? base + 4 * q : base + 4 * q + ((y >> 2) & 1) * 2 + ((x >> 2) & 1));
 }
-// block-diagonal composite of DCT blocks of size 2^l2 inside a 16x16 tile: C(r, k)
-__device__ __forceinline__ int pr_comp(const PReconLds& L, int l2, int r, int k) {
-  return (r >> l2) == (k >> l2) ? (int)L.T[(r & ((1 << l2) - 1)) << (5 - l2)][k & ((1 << l2) - 1)] : 0;
-}
 // a TB whose only non-zero level is a lone +-1 outside DC is dropped (tv code_tb, inter)
 __device__ __forceinline__ bool pr_zeroed(const PReconLds& L, int id) {
   return L.nz[id] == 0 || (L.nz[id] == 1 && L.sa[id] == 1 && L.dc[id] == 0);
 }
 
-// 7 waves per SIMD: 72 VGPRs and no scratch (8 would need 64 and spills).
+// 7 waves per SIMD: 72 VGPRs and no scratch (8 would need 64 and spills), and 7 workgroups
+// of PReconLds (22096 B) are what fits the CU's 160 KiB of LDS.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) k_inter_recon(FrameSet src, FrameSet ref, const uint8_t* phase,
                                                      FrameSet rec, DecisionSet dec, Geo g,
                                                      FrameSet ref1, const uint8_t* phase1) {
@@ -919,7 +936,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
   const int qpc = chroma_qp(qp, 0), Wc = g.W >> 1, Hc = g.H >> 1;
   const long W = g.W;  // the luma pitch, widened once up here (stays scalar: no spill at 72 VGPRs)
   __shared__ PReconLds L;
-  for (int i = tid; i < 1024; i += 256) L.T[i >> 5][i & 31] = (int16_t)kDct32.m[i >> 5][i & 31];
+  for (int i = tid; i < (int)(sizeof(TbFragTables) / 16); i += 256)
+    reinterpret_cast<uint4*>(&L.F)[i] = reinterpret_cast<const uint4*>(&kTbFragDev)[i];
   if (tid < 16) {
     const long u = ub + (long)((cy >> 3) + (tid >> 2)) * g.w8 + (cx >> 3) + (tid & 3);
     L.mv[tid][0] = dec.mv[2 * u];
@@ -1125,99 +1143,124 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
   // tile t: luma (whole: 32x32 tile ti,tj = t>>1, t&1; else quadrant t) for t < 4, chroma
   // (whole: plane t-4 as one 16x16 TB; else the Cb|Cr pair of quadrant t-4) for t >= 4.
   // ---------------------------------------------------------------- stage 1: T * R
+  // A lane's place in a fragment: operand row / column fi, K-run kq (tv/tb_frag.h); its four
+  // outputs are columns 4 * kq + r of row fi (tb_coder.h frag_tile).  The Cb|Cr pair tile is
+  // block-diagonal in the data too: lane (fi, kq) of its data operand is inside a block iff
+  // pin, plane pp as a B operand, fi >> 3 as an A operand -- and its outputs are inside one
+  // iff pin, plane fi >> 3, row fi & 7, columns 4 * (kq & 1) + r.
+  const int fi = lane & 15, kq = lane >> 4;
+  const bool pin = (fi >> 3) == (kq >> 1);
+  const int pp = kq >> 1;
+  auto T32 = [&](int o, int tile) { return frag8(reinterpret_cast<const _Float16*>(&L.F.t32[o][16 * tile + fi][8 * kq])); };
+  auto C16 = [&](int l2, int o) { return frag4(reinterpret_cast<const _Float16*>(&L.F.c16[4 - l2][o][fi][4 * kq])); };
+  const h4 zero4 = {0, 0, 0, 0};
+  // a lane's four outputs (row y, columns x .. x + 3) into the split f16 images of a stage output
+  auto put_y = [&](int y, int x, const int* v) { frag_store_split(&L.tmpYh[y * kTmpYP + x], &L.tmpYl[y * kTmpYP + x], v); };
+  auto put_c = [&](int pl, int y, int x, const int* v) {
+    frag_store_split(&L.tmpCh[pl][y * kTmpCP + x], &L.tmpCl[pl][y * kTmpCP + x], v);
+  };
   for (int t = wave; t < ntiles; t += 4) {
     int o[4];
     if (t < 4) {
+      int sh1;
       if (whole) {
-        mfma_tile([&](int r, int k) { return (int)L.T[r][k]; }, [&](int k, int c) { return (int)L.resY[k * 32 + c]; },
-                  t >> 1, t & 1, 32, false, false, o);
+        h8 b;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) b[e] = (_Float16)L.resY[(8 * kq + e) * 32 + 16 * (t & 1) + fi];
+        frag_tile(T32(0, t >> 1), b, o);
+        sh1 = 4;
       } else {
         const int ox = (t & 1) * 16, oy = (t >> 1) * 16, l2 = L.qtype[t] == 1 ? 4 : 3;
-        mfma_tile([&](int r, int k) { return pr_comp(L, l2, r, k); },
-                  [&](int k, int c) { return (int)L.resY[(oy + k) * 32 + ox + c]; }, 0, 0, 16, false, false, o);
+        h4 b;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[e] = (_Float16)L.resY[(oy + 4 * kq + e) * 32 + ox + fi];
+        frag_tile(C16(l2, 0), b, o);
+        sh1 = l2 - 1;
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        const int y = whole ? 16 * (t >> 1) + rr : (t >> 1) * 16 + rr, x = whole ? 16 * (t & 1) + cc : (t & 1) * 16 + cc;
-        const int sh1 = pr_l2_luma(L, x, y) - 1;
-        L.tmpY[y * 33 + x] = (o[r] + (1 << (sh1 - 1))) >> sh1;
-      }
+      for (int r = 0; r < 4; ++r) o[r] = (o[r] + (1 << (sh1 - 1))) >> sh1;
+      put_y((t >> 1) * 16 + fi, (t & 1) * 16 + kq * 4, o);
     } else if (whole) {
       const int pl = t - 4;
-      mfma_tile([&](int r, int k) { return pr_comp(L, 4, r, k); }, [&](int k, int c) { return (int)L.resC[pl][k * 16 + c]; },
-                0, 0, 16, false, false, o);
+      h4 b;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        L.tmpC[pl][rr * 17 + cc] = (o[r] + 4) >> 3;  // 16-point: sh1 = 3
-      }
+      for (int e = 0; e < 4; ++e) b[e] = (_Float16)L.resC[pl][(4 * kq + e) * 16 + fi];
+      frag_tile(C16(4, 0), b, o);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = (o[r] + 4) >> 3;  // 16-point: sh1 = 3
+      put_c(pl, fi, kq * 4, o);
     } else {
       const int q = t - 4, ox = (q & 1) * 8, oy = (q >> 1) * 8, l2 = L.qtype[q] == 1 ? 3 : 2;
-      mfma_tile([&](int r, int k) { return pr_comp(L, l2, r, k); },
-                [&](int k, int c) {
-                  return (k >> 3) == (c >> 3) ? (int)L.resC[k >> 3][(oy + (k & 7)) * 16 + ox + (c & 7)] : 0;
-                },
-                0, 0, 16, false, false, o);
-      const int sh1 = l2 - 1;
+      h4 b;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        if ((rr >> 3) == (cc >> 3)) L.tmpC[rr >> 3][(oy + (rr & 7)) * 17 + ox + (cc & 7)] = (o[r] + (1 << (sh1 - 1))) >> sh1;
+      for (int e = 0; e < 4; ++e) b[e] = (_Float16)L.resC[pp][(oy + 4 * (kq & 1) + e) * 16 + ox + (fi & 7)];
+      frag_tile(C16(l2, 0), pin ? b : zero4, o);
+      const int sh1 = l2 - 1;
+      if (pin) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (o[r] + (1 << (sh1 - 1))) >> sh1;
+        put_c(fi >> 3, oy + (fi & 7), ox + 4 * (kq & 1), o);
       }
     }
   }
   __syncthreads();
   // ------------------------------------------------- stage 2: A * T^T + quantisation
-  auto emit_level = [&](int16_t* dst, int id, int l2, int q, int v, bool origin) {
-    const int sh2 = l2 + 6;
-    const int lev = quant_level((v + (1 << (sh2 - 1))) >> sh2, q, l2, false);
-    *dst = (int16_t)lev;
-    if (lev) {
-      if (atomicAdd(&L.nz[id], 1)) L.multi = 1;
-      atomicAdd(&L.sa[id], tv_abs(lev));
+  // One tile = TBs of one size: shift and quantiser parameters are computed once per tile
+  // (wave-uniform), the level by the 32-bit quant_fast (tv/tb_frag.h has the range proof).
+  // A lane's four outputs are columns x .. x + 3 (x a multiple of 4) of one row: one TB, as
+  // TBs are 4-aligned, so the levels are one 8-byte store, the TB statistics one pair of LDS
+  // atomics per lane, and only the first column can be the TB's origin.  multi: some TB has
+  // >= 2 levels -- this lane adds two, or finds the count already non-zero.
+  auto emit_levels = [&](int16_t* dst, int id, int sh2, const QuantParams& q, const int* v, bool origin) {
+    int cnt = 0, sum = 0, lev[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      lev[r] = quant_fast((v[r] + (1 << (sh2 - 1))) >> sh2, q);
+      cnt += lev[r] != 0;
+      sum += tv_abs(lev[r]);
     }
-    if (origin) L.dc[id] = lev;
+    *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)(lev[0] & 0xffff) | (uint32_t)lev[1] << 16,
+                                                (uint32_t)(lev[2] & 0xffff) | (uint32_t)lev[3] << 16);
+    if (origin) L.dc[id] = lev[0];
+    if (cnt) {
+      if (atomicAdd(&L.nz[id], cnt) | (cnt > 1)) L.multi = 1;
+      atomicAdd(&L.sa[id], sum);
+    }
   };
   for (int t = wave; t < ntiles; t += 4) {
     int o[4];
     if (t < 4) {
+      int l2;
       if (whole) {
-        mfma_tile([&](int r, int k) { return L.tmpY[r * 33 + k]; }, [&](int k, int c) { return (int)L.T[c][k]; },
-                  t >> 1, t & 1, 32, true, true, o);
+        const int ia = (16 * (t >> 1) + fi) * kTmpYP + 8 * kq;
+        frag_tile_split_a(frag8(&L.tmpYh[ia]), frag8(&L.tmpYl[ia]), T32(0, t & 1), o);
+        l2 = 5;
       } else {
-        const int ox = (t & 1) * 16, oy = (t >> 1) * 16, l2 = L.qtype[t] == 1 ? 4 : 3;
-        mfma_tile([&](int r, int k) { return L.tmpY[(oy + r) * 33 + ox + k]; },
-                  [&](int k, int c) { return pr_comp(L, l2, c, k); }, 0, 0, 16, true, true, o);
+        const int ox = (t & 1) * 16, oy = (t >> 1) * 16;
+        l2 = L.qtype[t] == 1 ? 4 : 3;
+        const int ia = (oy + fi) * kTmpYP + ox + 4 * kq;
+        frag_tile_split_a(frag4(&L.tmpYh[ia]), frag4(&L.tmpYl[ia]), C16(l2, 0), o);
       }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        const int y = (t >> 1) * 16 + rr, x = (t & 1) * 16 + cc;
-        const int l2 = pr_l2_luma(L, x, y), m = (1 << l2) - 1;
-        emit_level(&L.resY[y * 32 + x], pr_tb_luma(L, x, y), l2, qp, o[r], (x & m) == 0 && (y & m) == 0);
-      }
+      const QuantParams qy = quant_params(qp, l2);
+      const int m = (1 << l2) - 1, y = (t >> 1) * 16 + fi, x = (t & 1) * 16 + kq * 4;
+      const int id = whole ? 0 : 4 * t + (l2 == 3 ? (fi >> 3) * 2 + (kq >> 1) : 0);
+      emit_levels(&L.resY[y * 32 + x], id, l2 + 6, qy, o, (x & m) == 0 && (y & m) == 0);
     } else if (whole) {
       const int pl = t - 4;
-      mfma_tile([&](int r, int k) { return L.tmpC[pl][r * 17 + k]; }, [&](int k, int c) { return pr_comp(L, 4, c, k); },
-                0, 0, 16, true, true, o);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        emit_level(&L.resC[pl][rr * 16 + cc], 16 + 16 * pl, 4, qpc, o[r], rr == 0 && cc == 0);
-      }
+      const int ia = fi * kTmpCP + 4 * kq;
+      frag_tile_split_a(frag4(&L.tmpCh[pl][ia]), frag4(&L.tmpCl[pl][ia]), C16(4, 0), o);
+      emit_levels(&L.resC[pl][fi * 16 + kq * 4], 16 + 16 * pl, 10, quant_params(qpc, 4), o, lane == 0);
     } else {
       const int q = t - 4, ox = (q & 1) * 8, oy = (q >> 1) * 8, l2 = L.qtype[q] == 1 ? 3 : 2;
-      mfma_tile([&](int r, int k) {
-                  return (r >> 3) == (k >> 3) ? L.tmpC[r >> 3][(oy + (r & 7)) * 17 + ox + (k & 7)] : 0;
-                },
-                [&](int k, int c) { return pr_comp(L, l2, c, k); }, 0, 0, 16, true, true, o);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        if ((rr >> 3) != (cc >> 3)) continue;
-        const int pl = rr >> 3, x = ox + (cc & 7), y = oy + (rr & 7), m = (1 << l2) - 1;
-        emit_level(&L.resC[pl][y * 16 + x], pr_tb_chroma(L, pl, x, y), l2, qpc, o[r], (x & m) == 0 && (y & m) == 0);
+      // A(r = fi, k = 4 kq ..): inside plane fi >> 3's block iff pin; the read is in bounds either way
+      const int ia = (oy + (fi & 7)) * kTmpCP + ox + 4 * (kq & 1);
+      const h4 ahi = frag4(&L.tmpCh[fi >> 3][ia]), alo = frag4(&L.tmpCl[fi >> 3][ia]);
+      frag_tile_split_a(pin ? ahi : zero4, pin ? alo : zero4, C16(l2, 0), o);
+      const QuantParams qc = quant_params(qpc, l2);
+      if (pin) {
+        const int m = (1 << l2) - 1, pl = fi >> 3, y = oy + (fi & 7), x = ox + 4 * (kq & 1);
+        const int id = 16 + 16 * pl + 4 * q + (l2 == 2 ? ((fi >> 2) & 1) * 2 + (kq & 1) : 0);
+        emit_levels(&L.resC[pl][y * 16 + x], id, l2 + 6, qc, o, (x & m) == 0 && (y & m) == 0);
       }
     }
   }
@@ -1322,44 +1365,65 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
     int o[4];
     if (t < 4) {
       if (whole) {
-        mfma_tile([&](int r, int k) { return (int)L.T[k][r]; },
-                  [&](int k, int c) { return deq_fast(L.resY[k * 32 + c], dq5); }, t >> 1, t & 1, 32, true, false, o);
+        h8 bhi, blo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int d = deq_fast(L.resY[(8 * kq + e) * 32 + 16 * (t & 1) + fi], dq5);
+          bhi[e] = f16_hi(d), blo[e] = f16_lo(d);
+        }
+        frag_tile_split_b(T32(1, t >> 1), bhi, blo, o);
       } else {
         const int ox = (t & 1) * 16, oy = (t >> 1) * 16, l2 = L.qtype[t] == 1 ? 4 : 3;
         const DeqParams dql = deq_params(qp, l2);
-        mfma_tile([&](int r, int k) { return pr_comp(L, l2, k, r); },
-                  [&](int k, int c) { return deq_fast(L.resY[(oy + k) * 32 + ox + c], dql); }, 0, 0, 16, true, false, o);
+        h4 bhi, blo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int d = deq_fast(L.resY[(oy + 4 * kq + e) * 32 + ox + fi], dql);
+          bhi[e] = f16_hi(d), blo[e] = f16_lo(d);
+        }
+        frag_tile_split_b(C16(l2, 1), bhi, blo, o);
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int y = (t >> 1) * 16 + (lane >> 4) * 4 + r, x = (t & 1) * 16 + (lane & 15);
-        L.tmpY[y * 33 + x] = clip3(-32768, 32767, (o[r] + 64) >> 7);
-      }
+      for (int r = 0; r < 4; ++r) o[r] = clip3(-32768, 32767, (o[r] + 64) >> 7);
+      put_y((t >> 1) * 16 + fi, (t & 1) * 16 + kq * 4, o);
     } else if (whole) {
       const int pl = t - 4;
-      mfma_tile([&](int r, int k) { return pr_comp(L, 4, k, r); },
-                [&](int k, int c) { return deq_fast(L.resC[pl][k * 16 + c], dqc4); }, 0, 0, 16, true, false, o);
+      h4 bhi, blo;
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        L.tmpC[pl][((lane >> 4) * 4 + r) * 17 + (lane & 15)] = clip3(-32768, 32767, (o[r] + 64) >> 7);
+      for (int e = 0; e < 4; ++e) {
+        const int d = deq_fast(L.resC[pl][(4 * kq + e) * 16 + fi], dqc4);
+        bhi[e] = f16_hi(d), blo[e] = f16_lo(d);
+      }
+      frag_tile_split_b(C16(4, 1), bhi, blo, o);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = clip3(-32768, 32767, (o[r] + 64) >> 7);
+      put_c(pl, fi, kq * 4, o);
     } else {
       const int q = t - 4, ox = (q & 1) * 8, oy = (q >> 1) * 8, l2 = L.qtype[q] == 1 ? 3 : 2;
       const DeqParams dqcl = deq_params(qpc, l2);
-      mfma_tile([&](int r, int k) { return pr_comp(L, l2, k, r); },
-                [&](int k, int c) {
-                  return (k >> 3) == (c >> 3) ? deq_fast(L.resC[k >> 3][(oy + (k & 7)) * 16 + ox + (c & 7)], dqcl) : 0;
-                },
-                0, 0, 16, true, false, o);
+      h4 bhi, blo;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        if ((rr >> 3) == (cc >> 3))
-          L.tmpC[rr >> 3][(oy + (rr & 7)) * 17 + ox + (cc & 7)] = clip3(-32768, 32767, (o[r] + 64) >> 7);
+      for (int e = 0; e < 4; ++e) {
+        const int d = deq_fast(L.resC[pp][(oy + 4 * (kq & 1) + e) * 16 + ox + (fi & 7)], dqcl);
+        bhi[e] = f16_hi(d), blo[e] = f16_lo(d);
+      }
+      frag_tile_split_b(C16(l2, 1), pin ? bhi : zero4, pin ? blo : zero4, o);
+      if (pin) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = clip3(-32768, 32767, (o[r] + 64) >> 7);
+        put_c(fi >> 3, oy + (fi & 7), ox + 4 * (kq & 1), o);
       }
     }
   }
   __syncthreads();
   // ------------------------------------- stage 4: G * T + prediction -> reconstruction
+  // a lane's four pixels (one row, 4-aligned) are one prediction dword and one dword store
+  auto recon4 = [&](uint32_t pw, const int* v) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w |= (uint32_t)clip_pixel((int)((pw >> (8 * r)) & 255u) + ((v[r] + 2048) >> 12)) << (8 * r);
+    return w;
+  };
   for (int t = wave; t < ntiles; t += 4) {
     int o[4];
     const bool tz = L.tzero[t];
@@ -1367,43 +1431,37 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
       o[0] = o[1] = o[2] = o[3] = 0;
     }
     if (t < 4) {
-      if (whole) {
-        if (!tz) mfma_tile([&](int r, int k) { return L.tmpY[r * 33 + k]; }, [&](int k, int c) { return (int)L.T[k][c]; },
-                  t >> 1, t & 1, 32, true, true, o);
+      if (tz) {  // o = 0
+      } else if (whole) {
+        const int ia = (16 * (t >> 1) + fi) * kTmpYP + 8 * kq;
+        frag_tile_split_a(frag8(&L.tmpYh[ia]), frag8(&L.tmpYl[ia]), T32(1, t & 1), o);
       } else {
         const int ox = (t & 1) * 16, oy = (t >> 1) * 16, l2 = L.qtype[t] == 1 ? 4 : 3;
-        if (!tz) mfma_tile([&](int r, int k) { return L.tmpY[(oy + r) * 33 + ox + k]; },
-                  [&](int k, int c) { return pr_comp(L, l2, k, c); }, 0, 0, 16, true, true, o);
+        const int ia = (oy + fi) * kTmpYP + ox + 4 * kq;
+        frag_tile_split_a(frag4(&L.tmpYh[ia]), frag4(&L.tmpYl[ia]), C16(l2, 1), o);
       }
-      uint8_t* R = rec.plane(0, b, g) + cy * W + cx;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int y = (t >> 1) * 16 + (lane >> 4) * 4 + r, x = (t & 1) * 16 + (lane & 15);
-        R[y * W + x] = (uint8_t)clip_pixel((int)L.predY[y * 32 + x] + ((o[r] + 2048) >> 12));
-      }
+      const int y = (t >> 1) * 16 + fi, x = (t & 1) * 16 + kq * 4;
+      *reinterpret_cast<uint32_t*>(rec.plane(0, b, g) + (cy + y) * W + cx + x) =
+          recon4(*reinterpret_cast<const uint32_t*>(&L.predY[y * 32 + x]), o);
     } else if (whole) {
       const int pl = t - 4;
-      if (!tz) mfma_tile([&](int r, int k) { return L.tmpC[pl][r * 17 + k]; }, [&](int k, int c) { return pr_comp(L, 4, k, c); },
-                0, 0, 16, true, true, o);
-      uint8_t* R = rec.plane(1 + pl, b, g) + (long)(cy >> 1) * Wc + (cx >> 1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int y = (lane >> 4) * 4 + r, x = lane & 15;
-        R[(long)y * Wc + x] = (uint8_t)clip_pixel((int)L.predC[pl][y * 16 + x] + ((o[r] + 2048) >> 12));
+      if (!tz) {
+        const int ia = fi * kTmpCP + 4 * kq;
+        frag_tile_split_a(frag4(&L.tmpCh[pl][ia]), frag4(&L.tmpCl[pl][ia]), C16(4, 1), o);
       }
+      *reinterpret_cast<uint32_t*>(rec.plane(1 + pl, b, g) + (long)((cy >> 1) + fi) * Wc + (cx >> 1) + kq * 4) =
+          recon4(*reinterpret_cast<const uint32_t*>(&L.predC[pl][fi * 16 + kq * 4]), o);
     } else {
       const int q = t - 4, ox = (q & 1) * 8, oy = (q >> 1) * 8, l2 = L.qtype[q] == 1 ? 3 : 2;
-      if (!tz) mfma_tile([&](int r, int k) {
-                  return (r >> 3) == (k >> 3) ? L.tmpC[r >> 3][(oy + (r & 7)) * 17 + ox + (k & 7)] : 0;
-                },
-                [&](int k, int c) { return pr_comp(L, l2, k, c); }, 0, 0, 16, true, true, o);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = (lane >> 4) * 4 + r, cc = lane & 15;
-        if ((rr >> 3) != (cc >> 3)) continue;
-        const int pl = rr >> 3, x = ox + (cc & 7), y = oy + (rr & 7);
-        rec.plane(1 + pl, b, g)[(long)((cy >> 1) + y) * Wc + (cx >> 1) + x] =
-            (uint8_t)clip_pixel((int)L.predC[pl][y * 16 + x] + ((o[r] + 2048) >> 12));
+      if (!tz) {
+        const int ia = (oy + (fi & 7)) * kTmpCP + ox + 4 * (kq & 1);
+        const h4 ahi = frag4(&L.tmpCh[fi >> 3][ia]), alo = frag4(&L.tmpCl[fi >> 3][ia]);
+        frag_tile_split_a(pin ? ahi : zero4, pin ? alo : zero4, C16(l2, 1), o);
+      }
+      if (pin) {
+        const int pl = fi >> 3, y = oy + (fi & 7), x = ox + 4 * (kq & 1);
+        *reinterpret_cast<uint32_t*>(rec.plane(1 + pl, b, g) + (long)((cy >> 1) + y) * Wc + (cx >> 1) + x) =
+            recon4(*reinterpret_cast<const uint32_t*>(&L.predC[pl][y * 16 + x]), o);
       }
     }
   }

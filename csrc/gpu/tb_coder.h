@@ -7,8 +7,14 @@
 // are split as v = 256*hi + lo and accumulated in two chains, so each chain's partial sums
 // are < 2^24 and the int32 recombination is bit-identical to the scalar golden model
 // (tv::forward_transform / tv::inverse_transform).  4- and 8-point TBs use the VALU.
+//
+// Two forms of the tile: mfma_tile gathers both operands element by element through
+// callables (wg_code_tb here, wave_code_tb, the AV1 transforms); frag_tile* takes operands
+// that already are f16 fragments in lane order (k_inter_recon: constant DCT tables of
+// tv/tb_frag.h, intermediates stored as split f16 by the stage that produces them).
 #pragma once
 #include "gpu_common.h"
+#include "tv/tb_frag.h"
 
 namespace tv {
 namespace gpu {
@@ -87,6 +93,57 @@ __device__ __forceinline__ void mfma_tile(FX X, FY Y, int ti, int tj, int K, boo
 #endif
 #pragma unroll
   for (int r = 0; r < 4; ++r) out[r] = split ? (int)hi[r] * 256 + (int)lo[r] : (int)hi[r];
+}
+
+// Fragment form of the same tile (k_inter_recon): the operands arrive as the lane's ready f16
+// K-run -- 8 halves for K = 32, 4 for K = 16 (tv/tb_frag.h has the lane layout) -- read with
+// one 16- or 8-byte LDS load from an image its producer stored in that order, so no operand
+// is marshalled element by element.  The split operand comes as two fragments (hi, lo with
+// v = 256 * hi + lo); the exactness argument is the one above.
+//
+// The instruction is issued with its operands swapped, P^T = B^T * A^T (an A fragment of row
+// n and a B fragment of column n are the same registers), so lane (fi = lane & 15, kq =
+// lane >> 4) receives out[r] = P(fi, 4 * kq + r): four consecutive columns of ONE row, which
+// its epilogue stores with one 8-byte (f16, int16) or 4-byte (pixel) access.
+__device__ __forceinline__ h8 frag8(const _Float16* p) { return *reinterpret_cast<const h8*>(p); }
+__device__ __forceinline__ h4 frag4(const _Float16* p) { return *reinterpret_cast<const h4*>(p); }
+__device__ __forceinline__ f32x4 frag_mfma(h8 a, h8 b) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 frag_mfma(h4 a, h4 b) {
+  return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+}
+// out = A * B, no split
+template <class H>
+__device__ __forceinline__ void frag_tile(H a, H b, int out[4]) {
+  const f32x4 p = frag_mfma(b, a);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) out[r] = (int)p[r];
+}
+// out = (256 * Ahi + Alo) * B
+template <class H>
+__device__ __forceinline__ void frag_tile_split_a(H ahi, H alo, H b, int out[4]) {
+  const f32x4 hi = frag_mfma(b, ahi), lo = frag_mfma(b, alo);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) out[r] = (int)hi[r] * 256 + (int)lo[r];
+}
+// out = A * (256 * Bhi + Blo)
+template <class H>
+__device__ __forceinline__ void frag_tile_split_b(H a, H bhi, H blo, int out[4]) {
+  const f32x4 hi = frag_mfma(bhi, a), lo = frag_mfma(blo, a);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) out[r] = (int)hi[r] * 256 + (int)lo[r];
+}
+// the 8-bit halves of v as f16: v = 256 * hi + lo, hi signed, lo in 0..255
+__device__ __forceinline__ _Float16 f16_hi(int v) { return (_Float16)(short)(v >> 8); }
+__device__ __forceinline__ _Float16 f16_lo(int v) { return (_Float16)(short)(v & 255); }
+// a lane's four outputs into the split f16 images of a stage output (8-byte aligned)
+__device__ __forceinline__ void frag_store_split(_Float16* hi, _Float16* lo, const int v[4]) {
+  h4 a, b;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[r] = f16_hi(v[r]), b[r] = f16_lo(v[r]);
+  *reinterpret_cast<h4*>(hi) = a;
+  *reinterpret_cast<h4*>(lo) = b;
 }
 
 // Run a stage over the whole N x N output: each wave owns 16x16 tiles; N <= 8 uses VALU.
