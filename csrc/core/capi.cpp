@@ -55,6 +55,9 @@ void tv_synth_frame(uint32_t seed, int t, int W, int H, uint8_t* y, uint8_t* u, 
   }
 }
 
+// tv::satd8x8 (tv/me_model.h) of one 8x8 block of differences, for the tests
+int tv_satd8x8(const int* d, int stride) { return satd8x8(d, stride); }
+
 // ------------------------------------ CPU encoder ---------------------------------------
 void* tv_cpu_encoder_new(int width, int height, int qp, int deblock, int range, int max_merge) {
   SeqConfig cfg;

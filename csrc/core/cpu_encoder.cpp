@@ -25,33 +25,6 @@ namespace tv {
 
 namespace {
 
-int satd8x8(const int* d, int stride) {
-  int m[64];
-  for (int j = 0; j < 8; ++j)
-    for (int i = 0; i < 8; ++i) m[j * 8 + i] = d[j * stride + i];
-  for (int j = 0; j < 8; ++j) {  // horizontal butterflies
-    int* r = m + j * 8;
-    for (int s = 1; s < 8; s <<= 1)
-      for (int i = 0; i < 8; ++i)
-        if (!(i & s)) {
-          const int a = r[i], b = r[i + s];
-          r[i] = a + b;
-          r[i + s] = a - b;
-        }
-  }
-  for (int i = 0; i < 8; ++i)  // vertical
-    for (int s = 1; s < 8; s <<= 1)
-      for (int j = 0; j < 8; ++j)
-        if (!(j & s)) {
-          const int a = m[j * 8 + i], b = m[(j + s) * 8 + i];
-          m[j * 8 + i] = a + b;
-          m[(j + s) * 8 + i] = a - b;
-        }
-  int sum = 0;
-  for (int k = 0; k < 64; ++k) sum += tv_abs(m[k]);
-  return (sum + 2) >> 2;
-}
-
 int block_satd(const uint8_t* src, int ss, const int* pred, int N) {
   int diff[32 * 32];
   for (int j = 0; j < N; ++j)
@@ -234,6 +207,18 @@ void me_ctb(const SeqConfig& cfg, const Picture& src, const Picture& ref, const 
         s += tv_abs(S[(size_t)(y + j) * W + x + i] - mc_luma_sample(R, W, W, H, bx + i, by + j, fx, fy));
     return s;
   };
+  auto satd_qpel = [&](int x, int y, int N, int mvx, int mvy) {  // sum of the block's 8x8 SATDs
+    int s = 0, d[64];
+    const int fx = mvx & 3, fy = mvy & 3, bx = x + (mvx >> 2), by = y + (mvy >> 2);
+    for (int gy = 0; gy < N; gy += 8)
+      for (int gx = 0; gx < N; gx += 8) {
+        for (int j = 0; j < 8; ++j)
+          for (int i = 0; i < 8; ++i)
+            d[j * 8 + i] = S[(size_t)(y + gy + j) * W + x + gx + i] - mc_luma_sample(R, W, W, H, bx + gx + i, by + gy + j, fx, fy);
+        s += satd8x8(d, 8);
+      }
+    return s;
+  };
   const int lim = range - 4;
   const int cx = cxi * kCtb, cy = cyi * kCtb;
   const int u0 = (cy >> 3) * w8 + (cx >> 3);
@@ -269,6 +254,31 @@ void me_ctb(const SeqConfig& cfg, const Picture& src, const Picture& ref, const 
     out.cost[bi] = (int)(best[bi] >> 11);
     int bx, by, n;
     me_blk(bi, bx, by, n);
+    if (cfg.subpel_satd) {
+      // the SATD sub-pel decision of tv/me_model.h: J = SATD + MV rate picks the vector, the
+      // reported cost stays SAD + MV rate at that vector
+      const int m0x = bmv[0], m0y = bmv[1];
+      int jbest = me_subpel_j(satd_qpel(cx + bx, cy + by, n, m0x, m0y), penmv, m0x, m0y, pmv);
+      for (int step = 2; step >= 1; step >>= 1) {
+        const int c0x = bmv[0], c0y = bmv[1];
+        unsigned key = me_subpel_key(jbest, 0);
+        for (int k = 0; k < 8; ++k) {
+          int ox, oy;
+          me_cand_offset(k, ox, oy);
+          const int qx = c0x + ox * step, qy = c0y + oy * step;
+          const unsigned v = me_subpel_key(me_subpel_j(satd_qpel(cx + bx, cy + by, n, qx, qy), penmv, qx, qy, pmv), k + 1);
+          if (v < key) {
+            key = v;
+            bmv[0] = qx;
+            bmv[1] = qy;
+          }
+        }
+        jbest = (int)(key >> 4);
+      }
+      out.pen[bi] = penmv[me_pen_index(bmv[0] - pmv[0], bmv[1] - pmv[1])];
+      if (bmv[0] != m0x || bmv[1] != m0y) out.cost[bi] = sad_qpel(cx + bx, cy + by, n, bmv[0], bmv[1]) + out.pen[bi];
+      continue;
+    }
     // half then quarter pel refinement (centre wins ties, then the lowest neighbour)
     for (int step = 2; step >= 1; step >>= 1) {
       const int c0x = bmv[0], c0y = bmv[1];

@@ -339,6 +339,8 @@ class Core {
     seq_.cascade = (c.deblock & 64) != 0;
     seq_.rdoq = !(c.deblock & 128);
     g_.rdoq = seq_.rdoq ? kRdoqMode : 0;
+    seq_.subpel_satd = (c.deblock & 256) != 0;
+    g_.subpel_satd = seq_.subpel_satd ? 1 : 0;
     seq_.mgop = c.mgop;
     if (c.mgop > 1) {
       const GopPlan gp = plan_gop(2 * c.mgop + 1, c.mgop);

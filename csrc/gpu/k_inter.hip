@@ -237,6 +237,23 @@ __global__ void __launch_bounds__(64) k_coarse_me(const uint8_t* qcur, const uin
 // The MV-rate table (Penalties::mv, 64 ints) is staged in LDS: the integer search and the
 // sub-pel argmin read it per candidate.  8 waves per SIMD (<= 64 VGPRs): the LDS fits 8 CTBs
 // per CU as well.
+//
+// kSatd (SeqConfig::subpel_satd, "SATD sub-pel decision" of tv/me_model.h): the two sub-pel
+// rounds score every (8x8 group, candidate) cell by Hadamard SATD as well as SAD, on the matrix
+// cores.  A 16x16 tile X holds four independent 8x8 cells of source - prediction; with
+// Hbd = diag(H8, H8), Z = Hbd * (X * Hbd) transforms all four at once in two
+// v_mfma_f32_16x16x16f16.  Operand maps (lane l, e / r = 0..3): A[row l & 15][k = 4 (l >> 4) + e],
+// B[k = 4 (l >> 4) + e][col l & 15], C[row 4 (l >> 4) + r][col l & 15].  A lane's A fragment of X
+// is 4 adjacent pixels of one row: one source dword of s32 minus 4 phase-plane samples.
+// Y = X * Hbd comes out in the C map, which is the B map, so it feeds Hbd * Y without any
+// lane movement, and Hbd is symmetric, so one constant fragment serves as B of the first and A
+// of the second product.  |X| <= 255, |Y| <= 2040 (exact in f16), |Z| <= 16320 (exact in
+// f32).  A lane loads the cell (row half (l >> 3) & 1, column half l >> 5) and ends with Z of
+// the cell (row half l >> 5, column half (l >> 3) & 1); both lane sets are 8 lanes of a DPP
+// half-row in two adjacent 16-lane rows, so SAD and SATD reduce the same way.  The per-cell
+// tables live in the candidate windows' LDS, dead after the integer search.
+__device__ __forceinline__ uint32_t phase4(const uint8_t* P, const Geo& g, int x, int y);
+template <bool kSatd>
 __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) k_inter_me(FrameSet src, FrameSet ref, const uint8_t* phase,
                                                          DecisionSet dec, const int16_t* prev_mv, const int16_t* cmv,
                                                          Geo g, const RcTables* rc, int range,
@@ -480,8 +497,142 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
       }
     }
   };
+  // kSatd: per-cell tables [group r][position p] of one round (np positions: the centre and
+  // the 8 neighbours in the half-pel round, the 8 neighbours in the quarter-pel round), the
+  // blocks' running J between the rounds, and the round's cell descriptors
+  int* const cellsatd = reinterpret_cast<int*>(win);
+  int* const cellsad = cellsatd + NC * 9;
+  int* const jbest = cellsad + NC * 9;
+  int* const celld = jbest + 21;  // 2 ints per cell
+  static_assert(4 * NC * 9 + 21 <= kMeMaxCand * kWinCand, "cell tables fit the window LDS");
+  static_assert((NC * 9) % 4 == 0 && (NC * 8) % 4 == 0, "whole tiles");
+  auto satd_tiles = [&](int step, auto NP) {
+    constexpr int np = decltype(NP)::value;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // One thread per cell decodes it once (every lane of a tile doing so was most of the
+    // instructions of the round): d0 = x of the cell's left sample + 1024 | plane << 16 |
+    // source word << 20 | source row << 23, d1 = y of its top row.
+    for (int c = tid; c < NC * np; c += kMeThreads) {
+      const int r = c / np, p = c - r * np;
+      int bi, row0, col0;
+      grp_geom(r, bi, row0, col0);
+      int bx, by, l2b;
+      me_blk_geom(bi, bx, by, l2b);
+      const int k = p + 8 - np;  // neighbour index, -1 the centre (half-pel round only)
+      int ox = 0, oy = 0;
+      if (k >= 0) me_cand_offset(k, ox, oy);
+      const int mx = bmv[bi][0] + ox * step, my = bmv[bi][1] + oy * step;
+      const int gx0 = cx + bx + col0 + (mx >> 2);  // >= -range - 8 > -1024, < 2^16 - 1024 for any picture
+      celld[2 * c] = (gx0 + 1024) | ((mx & 3) + 4 * (my & 3)) << 16 | ((bx + col0) >> 2) << 20 | (by + row0) << 23;
+      celld[2 * c + 1] = cy + by + row0 + (my >> 2);
+    }
+    __syncthreads();
+    const int i = lane & 15, kq = lane >> 4;
+    h4 hb;  // Hbd[l & 15][4 (l >> 4) + e]
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k = 4 * kq + e;
+      hb[e] = (i >> 3) == (k >> 3) ? (_Float16)me_h8(i & 7, k & 7) : (_Float16)0;
+    }
+    const int cin = ((lane >> 3) & 1) + 2 * (lane >> 5), cout = (lane >> 5) + 2 * ((lane >> 3) & 1);
+    const int j = lane & 7, w = kq & 1;  // my row and dword of the cell I load
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    // bytes (b0, b1) or (b2, b3) of v as the f16 pair (1024 + b, 1024 + b'): 0x6400 | b
+    auto f16_lo = [](uint32_t v) { return __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, v, 0x04010400u)); };
+    auto f16_hi = [](uint32_t v) { return __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, v, 0x04030402u)); };
+    auto pk = [](float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b)); };
+    // A wave takes its tiles T at a time (27 or 24 per wave): the T phase-plane dword pairs
+    // are loaded first, then T independent MFMA chains.  The address clamps like the planes'
+    // own border rule, which is exact for the rows; samples left or right of the padded plane
+    // need the per-byte clamp: patched in between, which a wave away from the picture's sides
+    // skips.
+    constexpr int T = 3, nw = kMeThreads / 64, ntiles = NC * np / 4;
+    static_assert(ntiles % (T * nw) == 0, "whole chunks");
+    for (int t0 = wv; t0 < ntiles; t0 += T * nw) {  // wave-uniform
+      uint32_t pv[T], sv[T];
+      unsigned clampx = 0;  // tiles whose samples need the per-byte path
+#pragma unroll
+      for (int n = 0; n < T; ++n) {
+        const int c = 4 * (t0 + n * nw) + cin, d0 = celld[2 * c], gy = celld[2 * c + 1] + j;
+        const int gx = (d0 & 0xffff) - 1024 + 4 * w, a = gx & ~3;
+        clampx |= (gx >= -8 && a <= g.W ? 0u : 1u) << n;
+        const uint8_t* P = ph + (long)((d0 >> 16) & 15) * g.psz;
+        const uint32_t* q =
+            reinterpret_cast<const uint32_t*>(P + (long)(clip3(-8, g.H + 7, gy) + 8) * g.pw16 + clip3(-8, g.W, a) + 8);
+        pv[n] = __builtin_amdgcn_alignbyte(q[1], q[0], (unsigned)(gx & 3));
+        sv[n] = s32[src_word(((d0 >> 23) & 31) + j, ((d0 >> 20) & 7) + w)];
+      }
+      if (__builtin_amdgcn_ballot_w64(clampx != 0)) {
+#pragma unroll
+        for (int n = 0; n < T; ++n) {
+          if (!((clampx >> n) & 1u)) continue;
+          const int c = 4 * (t0 + n * nw) + cin, d0 = celld[2 * c], gy = celld[2 * c + 1] + j;
+          const int gx = (d0 & 0xffff) - 1024 + 4 * w;
+          const uint8_t* P = ph + (long)((d0 >> 16) & 15) * g.psz;
+          uint32_t v = 0;
+          for (int e = 0; e < 4; ++e) v |= (uint32_t)phase_at(P, g, gx + e, gy) << (8 * e);
+          pv[n] = v;
+        }
+      }
+#pragma unroll
+      for (int n = 0; n < T; ++n) {
+        // source - prediction in f16: (1024 + s) - (1024 + p), exact
+        const h2 xl = f16_lo(sv[n]) - f16_lo(pv[n]), xh = f16_hi(sv[n]) - f16_hi(pv[n]);
+        const h4 x = {xl[0], xl[1], xh[0], xh[1]};
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 y = __builtin_amdgcn_mfma_f32_16x16x16f16(x, hb, zero, 0, 0, 0);
+        const h4 yh = __builtin_bit_cast(h4, make_uint2(pk(y[0], y[1]), pk(y[2], y[3])));  // |y| <= 2040: exact
+        const f32x4 z = __builtin_amdgcn_mfma_f32_16x16x16f16(hb, yh, zero, 0, 0, 0);
+        // One reduction for both: a cell's sum of |Z| is at most sqrt(64 * sum Z^2) = sqrt(64 *
+        // 64 * sum d^2) <= 512 * 255 < 2^17, its SAD at most 64 * 255 < 2^14.
+        int v = (int)(__builtin_fabsf(z[0]) + __builtin_fabsf(z[1]) + __builtin_fabsf(z[2]) + __builtin_fabsf(z[3])) |
+                (int)__builtin_amdgcn_sad_u8(sv[n], pv[n], 0u) << 17;
+        v += dpp::mov<dpp::kQuadXor1>(v);  // the cell's 8 lanes x 2 rows; needs the full wave
+        v += dpp::mov<dpp::kQuadXor2>(v);
+        v += dpp::mov<dpp::kRowHalfMirror>(v);
+        const auto r16 = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+        const unsigned sum = r16[0] + r16[1];
+        // my lane set loaded cell cin (the SAD bits) and holds the transform of cell cout
+        if ((lane & 0x17) == 0) {
+          const int t = t0 + n * nw;
+          cellsad[4 * t + cin] = (int)(sum >> 17);
+          cellsatd[4 * t + cout] = (int)(((sum & 0x1ffffu) + 2) >> 2);
+        }
+      }
+    }
+  };
+  auto subpel_argmin_satd = [&](int step, int np) {
+    if (tid < 21) {
+      const int r0 = tid < 16 ? tid : (tid < 20 ? N8 + 4 * (tid - 16) : 2 * N8), ng = tid < 16 ? 1 : (tid < 20 ? 4 : 16);
+      auto blk = [&](const int* tab, int p) {
+        int s = 0;
+        for (int q = 0; q < ng; ++q) s += tab[(r0 + q) * np + p];
+        return s;
+      };
+      if (np == 9) jbest[tid] = me_subpel_j(blk(cellsatd, 0), penmv, bmv[tid][0], bmv[tid][1], pmv);
+      unsigned key = me_subpel_key(jbest[tid], 0);
+      for (int k = 0; k < 8; ++k) {
+        int ox, oy;
+        me_cand_offset(k, ox, oy);
+        const int mx = bmv[tid][0] + ox * step, my = bmv[tid][1] + oy * step;
+        const unsigned v = me_subpel_key(me_subpel_j(blk(cellsatd, k + np - 8), penmv, mx, my, pmv), k + 1);
+        key = v < key ? v : key;
+      }
+      const int kk = (int)(key & 15);
+      jbest[tid] = (int)(key >> 4);
+      if (kk) {  // the reported cost stays in the SAD domain: SAD + MV rate at the new vector
+        int ox, oy;
+        me_cand_offset(kk - 1, ox, oy);
+        bmv[tid][0] += ox * step;
+        bmv[tid][1] += oy * step;
+        bcost[tid] = blk(cellsad, kk - 1 + np - 8) + penmv[me_pen_index(bmv[tid][0] - pmv[0], bmv[tid][1] - pmv[1])];
+      }
+    }
+  };
   __syncthreads();  // bmv of the integer search
-  {
+  if constexpr (kSatd) {
+    satd_tiles(2, std::integral_constant<int, 9>{});
+  } else {
     // Half-pel round.  bmv is at integer pels, so the 8 neighbours lie on three phase planes
     // only: (+-2, 0) on plane fx = 2 at integer x - 1 and x, (0, +-2) on fy = 2 at rows y - 1
     // and y, the four diagonals on (2, 2) at both.  A wave takes one plane set, a lane one
@@ -581,7 +732,7 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
     }
   }
   __syncthreads();
-  subpel_argmin(2);
+  if constexpr (kSatd) subpel_argmin_satd(2, 9); else subpel_argmin(2);
   __syncthreads();  // bmv of the half-pel round
   // Quarter-pel round: the 8 neighbours lie on 8 different planes.  One wave per block class
   // (8x8, 16x16, 32x32 groups; the fourth wave goes straight to the barrier), a lane = one
@@ -589,7 +740,9 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
   // source rows once, then takes both candidates' SADs (per row 3 aligned dwords of the phase
   // plane, v_alignbyte, v_sad_u8) -- all 384 (group, candidate) cells in one pass.  A DPP row
   // is one pair's 16 groups, so the quad / row sums below are one block's.
-  {
+  if constexpr (kSatd) {
+    satd_tiles(1, std::integral_constant<int, 8>{});
+  } else {
     constexpr int step = 1;
     const int cls = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
     if (cls < 3) {
@@ -682,7 +835,7 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
     }
   }
   __syncthreads();
-  subpel_argmin(1);
+  if constexpr (kSatd) subpel_argmin_satd(1, 8); else subpel_argmin(1);
   __syncthreads();
 
   // B picture: hand this list's 21 block results to k_bi_decide
@@ -1513,7 +1666,7 @@ void launch_inter_frame(FrameSet src, FrameSet ref, const uint8_t* phase, FrameS
   const PIntraBuffers none{};
   if (pi && hipMemsetAsync(pi->count, 0, 6 * sizeof(int), s) != hipSuccess) return;
   const dim3 grid(g.wc * g.hc, B);
-  k_inter_me<<<grid, kMeThreads, 0, s>>>(src, ref, phase, dec, me.prev_mv, me.cmv, g, rc, range, nullptr, pi ? *pi : none);
+  (g.subpel_satd ? k_inter_me<true> : k_inter_me<false>)<<<grid, kMeThreads, 0, s>>>(src, ref, phase, dec, me.prev_mv, me.cmv, g, rc, range, nullptr, pi ? *pi : none);
   if (pi) launch_pintra_decide(src, dec, g, rc, *pi, B, s);
   k_inter_recon<<<grid, 256, 0, s>>>(src, ref, phase, rec, dec, g, FrameSet{}, nullptr);
   if (pi) launch_pintra_recon(src, rec, dec, g, *pi, B, s);
@@ -1525,8 +1678,9 @@ void launch_inter_frame_b(FrameSet src, FrameSet ref0, const uint8_t* phase0, Fr
   const dim3 grid(g.wc * g.hc, B);
   CtbMeOut* o1 = meout + (long)B * g.wc * g.hc;
   const PIntraBuffers none{};
-  k_inter_me<<<grid, kMeThreads, 0, s>>>(src, ref0, phase0, dec, me0.prev_mv, me0.cmv, g, rc, range[0], meout, none);
-  k_inter_me<<<grid, kMeThreads, 0, s>>>(src, ref1, phase1, dec, me1.prev_mv, me1.cmv, g, rc, range[1], o1, none);
+  const auto k_me = g.subpel_satd ? k_inter_me<true> : k_inter_me<false>;
+  k_me<<<grid, kMeThreads, 0, s>>>(src, ref0, phase0, dec, me0.prev_mv, me0.cmv, g, rc, range[0], meout, none);
+  k_me<<<grid, kMeThreads, 0, s>>>(src, ref1, phase1, dec, me1.prev_mv, me1.cmv, g, rc, range[1], o1, none);
   k_bi_decide<<<grid, 256, 0, s>>>(src, phase0, phase1, meout, o1, dec, g, rc);
   k_inter_recon<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, ref1, phase1);
 }

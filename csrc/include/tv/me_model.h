@@ -106,6 +106,58 @@ TV_HD void me_cand_offset(int k, int& ox, int& oy) {
   oy = k < 3 ? -1 : (k < 5 ? 0 : 1);
 }
 
+// ---- SATD sub-pel decision (SeqConfig::subpel_satd, flag bit 256; CPU == GPU) -----------
+// Off by default.  The integer search is unchanged: it gives the integer vector m0 of each
+// of the 21 blocks and cost = SAD + pen.  With the tool on, the half- and quarter-pel rounds
+// compare J(mv) = satd(mv) + penmv[me_pen_index(mv - pmv)], where satd(mv) is the sum over
+// the block's 8x8 groups (1 / 4 / 16) of satd8x8(source - prediction) on the same 8-bit MC
+// samples the SAD reads.  Jbest starts at J(m0) and carries from the half-pel round into the
+// quarter-pel round; each round tests the 8 neighbours (me_cand_offset order) of the vector
+// it started from, and a neighbour replaces the running best only when strictly smaller: the
+// centre wins ties, then the lowest k (me_subpel_key packs that order into one compare).
+// After both rounds the block reports SAD(mv) + pen(mv) of the final vector, so everything
+// downstream (CU split, intra-in-P gate, bi decision) reads SAD-domain costs as before.
+//
+// satd8x8 = (sum |H8 d H8| + 2) >> 2 with the Sylvester (natural-order) Hadamard matrix;
+// |d| <= 255 gives |H8 d| <= 2040 and |H8 d H8| <= 16320.
+TV_HD int satd8x8(const int* d, int stride) {
+  int m[64];
+  for (int j = 0; j < 8; ++j)
+    for (int i = 0; i < 8; ++i) m[j * 8 + i] = d[j * stride + i];
+  for (int j = 0; j < 8; ++j) {  // horizontal butterflies
+    int* r = m + j * 8;
+    for (int s = 1; s < 8; s <<= 1)
+      for (int i = 0; i < 8; ++i)
+        if (!(i & s)) {
+          const int a = r[i], b = r[i + s];
+          r[i] = a + b;
+          r[i + s] = a - b;
+        }
+  }
+  for (int i = 0; i < 8; ++i)  // vertical
+    for (int s = 1; s < 8; s <<= 1)
+      for (int j = 0; j < 8; ++j)
+        if (!(j & s)) {
+          const int a = m[j * 8 + i], b = m[(j + s) * 8 + i];
+          m[j * 8 + i] = a + b;
+          m[(j + s) * 8 + i] = a - b;
+        }
+  int sum = 0;
+  for (int k = 0; k < 64; ++k) sum += tv_abs(m[k]);
+  return (sum + 2) >> 2;
+}
+// entry (i, j) of the natural-order Hadamard matrix H8: +1 / -1 by the parity of popcount(i & j)
+TV_HD int me_h8(int i, int j) {
+  const int v = i & j;
+  return ((v ^ (v >> 1) ^ (v >> 2)) & 1) ? -1 : 1;
+}
+// the cost rule and the tie rule of one round: key = J << 4 | slot, slot 0 the round's
+// running best on entry, k + 1 neighbour k; the smallest key wins
+TV_HD int me_subpel_j(int satd, const int* penmv, int mx, int my, const int* pmv) {
+  return satd + penmv[me_pen_index(mx - pmv[0], my - pmv[1])];
+}
+TV_HD unsigned me_subpel_key(int j, int slot) { return ((unsigned)j << 4) | (unsigned)slot; }
+
 // ---- intra mode pre-selection (I-frame analysis, CPU == GPU) ---------------------------
 // stage 1: planar, DC and the angular modes 2, 6, 10, ..., 34 (11 modes); stage 2: the
 // +-1 / +-2 neighbours of the best stage-1 angular mode (never stage-1 modes themselves).

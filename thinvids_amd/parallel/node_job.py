@@ -1075,6 +1075,8 @@ def main(argv=None) -> int:
     ap.add_argument("--no-cascade", dest="cascade", action="store_false", help="HEVC: flat QP (no I P P P QP cascade)")
     ap.add_argument("--no-pintra", dest="pintra", action="store_false", help="HEVC: no intra CUs in P pictures")
     ap.add_argument("--no-rdoq", dest="rdoq", action="store_false", help="HEVC: no RDOQ-lite coefficient-group trimming")
+    ap.add_argument("--subpel-satd", dest="subpel_satd", action="store_true",
+                    help="HEVC: sub-pel motion vectors chosen by SATD + MV rate (off by default)")
     ap.add_argument("--deinterlace", action="store_true", help="bwdif every segment (DVD-native interlaced sources)")
     a = ap.parse_args(argv)
     import torch
@@ -1093,7 +1095,8 @@ def main(argv=None) -> int:
     ladder = [int(x) for x in a.ladder.split(",") if x.strip()] or None
     res = run_job(a.input, a.output, a.height, a.qp, a.gop, a.segment_frames, a.mode, a.bitrate_kbps, ladder,
                   software=a.software, resume_dir=a.resume_dir, max_retries=a.max_retries, bframes=a.bframes,
-                  tools={"wpp": a.wpp, "rqt": a.rqt, "pintra": a.pintra, "cascade": a.cascade, "rdoq": a.rdoq},
+                  tools={"wpp": a.wpp, "rqt": a.rqt, "pintra": a.pintra, "cascade": a.cascade, "rdoq": a.rdoq,
+                         **({"subpel_satd": True} if a.subpel_satd else {})},
                   deinterlace=a.deinterlace)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res), flush=True)

@@ -4,7 +4,8 @@
 
 Prints one JSON line per QP (kbps per 30 fps stream, PSNR-Y / YUV over the whole clip) and,
 with --anchor FILE (a previous run's output), the BD-rate against it.  The GPU engine is bit-
-exact with this encoder, so the curve is the engine's curve too.
+exact with this encoder, so the curve is the engine's curve too; --engine gpu runs the points on
+the GPU engine itself (its own synthetic source and SSE), which is what makes 1080p practical.
 """
 from __future__ import annotations
 
@@ -33,6 +34,10 @@ def run_point(args):
             fq.append(max(0, min(51, qp + (a["iqp"] if idr else cascade[(i % a["gop"] - 1) % len(cascade)]))))
     import numpy as np
 
+    kw = dict(sao=a["sao"], rqt=a["rqt"], pintra=a["pintra"], wpp=a["wpp"], cascade=a["ippp_cascade"], rdoq=a["rdoq"],
+              subpel_satd=a["subpel_satd"])
+    if a.get("engine") == "gpu":
+        return run_point_gpu(qp, a, w, h, seed, fq, kw)
     if a.get("codec") == "av1":
         from thinvids_amd.models import av1
 
@@ -48,7 +53,6 @@ def run_point(args):
             stream += r.stream
             ys += [hevc.psnr(f[0], rec[:W * H].reshape(H, W)[:h, :w]) for f, rec in zip(frames[s0:], r.recon)]
     else:
-        kw = dict(sao=a["sao"], rqt=a["rqt"], pintra=a["pintra"], wpp=a["wpp"], cascade=a["ippp_cascade"], rdoq=a["rdoq"])
         stream, recons = hevc.encode_sequence_cpu(frames, qp=qp, gop=a["gop"], frame_qps=fq, bframes=a["bframes"], **kw)
         ys = [hevc.psnr(f[0], r[0][:h, :w]) for f, r in zip(frames, recons)]
 
@@ -56,6 +60,29 @@ def run_point(args):
     py = -10 * np.log10(mse_y)
     kbps = len(stream) * 8 * 30 / len(frames) / 1000
     return {"qp": qp, "kbps": round(kbps, 2), "psnr_y": round(float(py), 4), "frames": len(frames)}
+
+
+def run_point_gpu(qp, a, w, h, seed, fq, kw):
+    """The same point on the GPU engine: one segment per GOP, PSNR-Y from the engine's SSE."""
+    import numpy as np
+
+    from thinvids_amd.models.gpu_engine import GpuEngine
+
+    if a.get("codec") == "av1":
+        raise SystemExit("--engine gpu is the HEVC engine")
+    n, gop = a["frames"], min(a["gop"], a["frames"])
+    if n % gop:
+        raise SystemExit("--engine gpu: --frames must be a multiple of --gop")
+    starts = list(range(0, n, gop))
+    eng = GpuEngine(w, h, qp=qp, batch=len(starts), gop=gop, seed=seed, bframes=a["bframes"], **kw)
+    try:
+        segs = eng.encode_synthetic(starts, gop, qp=None if fq is None else [fq[s:s + gop] for s in starts])
+        sse_y = sum(eng.sse(b)[0] for b in range(len(starts)))
+    finally:
+        eng.close()
+    py = float("inf") if sse_y == 0 else 10 * np.log10(255.0 ** 2 * w * h * n / sse_y)
+    kbps = sum(len(s) for s in segs) * 8 * 30 / n / 1000
+    return {"qp": qp, "kbps": round(kbps, 2), "psnr_y": round(float(py), 4), "frames": n}
 
 
 def main():
@@ -80,16 +107,22 @@ def main():
     ap.add_argument("--pintra", type=int, default=int(env_on("TV_PINTRA")))
     ap.add_argument("--wpp", type=int, default=int(env_on("TV_WPP")))
     ap.add_argument("--rdoq", type=int, default=1, help="RDOQ-lite coefficient-group trimming")
+    ap.add_argument("--subpel-satd", type=int, default=0, help="sub-pel vectors chosen by SATD + MV rate (tv/me_model.h)")
+    ap.add_argument("--engine", choices=("cpu", "gpu"), default="cpu", help="gpu: run the points on the GPU engine, one after another")
     ap.add_argument("--anchor", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     cfg = dict(res=a.res, frames=a.frames, gop=a.gop, sao=bool(a.sao), seed=a.seed, textured=a.textured,
                cascade=[int(x) for x in a.cascade.split(",")] if a.cascade else [], iqp=a.iqp,
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
-               ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq))
+               ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
+               engine=a.engine)
     qps = [int(q) for q in a.qps.split(",")]
-    with ProcessPoolExecutor(len(qps)) as ex:
-        pts = list(ex.map(run_point, [(q, cfg) for q in qps]))
+    if a.engine == "gpu":
+        pts = [run_point((q, cfg)) for q in qps]
+    else:
+        with ProcessPoolExecutor(len(qps)) as ex:
+            pts = list(ex.map(run_point, [(q, cfg) for q in qps]))
     for p in pts:
         print(json.dumps(p))
     if a.out:
