@@ -52,12 +52,15 @@ def test_key_frame_avif_decodes_exactly():
     _check(res.stream, res.tu_sizes, res.recon, w, h)
 
 
-@pytest.mark.parametrize("w,h,q", [(160, 96, 100), (200, 120, 60), (264, 200, 160)])
+@pytest.mark.parametrize("w,h,q", [(160, 96, 100), (200, 120, 60), (264, 200, 120)])
 def test_gop_avis_decodes_exactly(w, h, q):
     """Key + 15 inter frames, deblocking + CDEF + restoration on; 200x120 and 264x200 have
-    a render size smaller than the coded size and partial superblocks / restoration units."""
+    a render size smaller than the coded size and partial superblocks / restoration units.
+    (264x200 ran at q 160 until the restoration check counted real units only: there the
+    golden restores none; at q 120 it restores 22.)"""
     res = av1.golden_encode(_frames(7, w, h, 16), w, h, q)
-    assert (res.lr[..., 0] >= 0).any(), "restoration never used: the LR path is not exercised"
+    real = av1.lr_real_units(*av1.coded_size(w, h))  # chroma planes' padding entries are 0, not a set
+    assert (res.lr[..., 0] >= 0)[:, real].any(), "restoration never used: the LR path is not exercised"
     assert (res.fparams[:, 2] > 0).all(), "deblocking off"
     _check(res.stream, res.tu_sizes, res.recon, w, h)
 

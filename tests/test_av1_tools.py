@@ -313,3 +313,76 @@ def test_gpu_txfm_bit_exact():
         ig = av1.txfm2d(cg, col, row, inverse=True)
         np.testing.assert_array_equal(ig.cpu().numpy(), av1.txfm2d(cc, col, row, inverse=True),
                                       err_msg=f"inv {n} {col} {row}")
+
+
+# ------------------------------------------------------------ transform extremes -------
+def _txfm_model(x, col, row, inverse):
+    """numpy int64 model of txfm2d: two integer matrix products with the 1-D bases, each
+    followed by the round-shift of av1_txfm.h txfm_shifts and a clamp to int16.  Returns
+    (output, number of stage-1 values at a clamp, number of outputs at a clamp)."""
+    n = x.shape[-1]
+    lg = n.bit_length() - 1
+    f1, f2 = 12 + (lg - 1) // 2 - 2, 12 + lg // 2 - 1
+    i1, i2 = 13 + lg // 2, 14 + (lg - 1) // 2
+    bc, br = av1.txfm_basis(col, n).astype(np.int64), av1.txfm_basis(row, n).astype(np.int64)
+    rs = lambda v, s: (v + (1 << (s - 1))) >> s  # noqa: E731
+    x = x.astype(np.int64)
+    if not inverse:
+        raw1 = rs(bc @ x, f1)               # columns: tmp = Bc X
+        t = np.clip(raw1, -32768, 32767)
+        raw2 = rs(t @ br.T, f2)             # rows: C = tmp Br^T
+    else:
+        raw1 = rs(x @ br, i1)               # rows: g = C Br
+        t = np.clip(raw1, -32768, 32767)
+        raw2 = rs(bc.T @ t, i2)             # columns: X = Bc^T g
+    out = np.clip(raw2, -32768, 32767)
+    return out.astype(np.int16), int((raw1 != t).sum()), int((raw2 != out).sum())
+
+
+def _txfm_extreme_blocks(n, col, row):
+    """20 blocks at the ends of the input range: constants, and for basis functions k in
+    {0, 1, N/2, N-1} the sign pattern that maximises |coefficient k| of both 1-D passes,
+    at +-255 (9-bit residuals) and at the int16 limits."""
+    bc, br = av1.txfm_basis(col, n), av1.txfm_basis(row, n)
+    out = [np.full((n, n), v, np.int64) for v in (255, -255, 32767, -32768)]
+    for k in (0, 1, n // 2, n - 1):
+        s = np.outer(np.sign(bc[k]), np.sign(br[k])).astype(np.int64)
+        out += [255 * s, -255 * s,
+                np.where(s > 0, 32767, np.where(s < 0, -32768, 0)),
+                np.where(s > 0, -32768, np.where(s < 0, 32767, 0))]
+    return np.stack(out).astype(np.int16)
+
+
+def _txfm_calls(blocks):
+    """Stacks of 17 blocks and of 1 block (the small kernel's workgroups hold 16 4x4 or four
+    8x8 blocks: 17 leaves a partial last workgroup)."""
+    return [blocks[:17]] + [blocks[i:i + 1] for i in range(17, len(blocks))]
+
+
+def test_txfm_extremes_match_int64_model():
+    stage1 = {False: 0, True: 0}
+    final = {False: 0, True: 0}
+    for n, col, row in _TX:
+        blocks = _txfm_extreme_blocks(n, col, row)
+        for inverse in (False, True):
+            want, c1, c2 = _txfm_model(blocks, col, row, inverse)
+            got = np.concatenate([av1.txfm2d(x, col, row, inverse=inverse) for x in _txfm_calls(blocks)])
+            np.testing.assert_array_equal(got, want, err_msg=f"{'inv' if inverse else 'fwd'} {n} {col} {row}")
+            stage1[inverse] += c1
+            final[inverse] += c2
+            assert not c2 or np.isin(got, (-32768, 32767)).any()
+    # the inputs reach clamp16 in both stages of both directions
+    assert all(stage1.values()) and all(final.values()), (stage1, final)
+
+
+@pytest.mark.gpu
+def test_gpu_txfm_extremes_bit_exact():
+    import torch
+
+    for n, col, row in _TX:
+        blocks = _txfm_extreme_blocks(n, col, row)
+        for inverse in (False, True):
+            for x in _txfm_calls(blocks):
+                got = av1.txfm2d(torch.from_numpy(x).cuda(), col, row, inverse=inverse).cpu().numpy()
+                np.testing.assert_array_equal(got, av1.txfm2d(x, col, row, inverse=inverse),
+                                              err_msg=f"{'inv' if inverse else 'fwd'} {n} {col} {row} nblk {len(x)}")
