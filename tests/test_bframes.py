@@ -252,7 +252,6 @@ def test_amvp_spatial_scaling_matches_spec_formula():
     from thinvids_amd._native import core_lib
 
     f = core_lib().tv_hevc_scale_mv
-    f.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)]
     rng = np.random.default_rng(3)
     out = (C.c_int * 2)()
     cases = [((7, -3), 2, -2), ((-64, 33), -4, 4), ((1, 1), 1, 3), ((5000, -4000), 3, -1), ((-1, 0), -8, 7),

@@ -31,7 +31,6 @@ def _ip(a):
 
 def expand(which):
     lib = core_lib()
-    lib.tv_tb_frag_expand.restype = C.c_int
     out = np.full(1024, 12345, np.int32)
     side = lib.tv_tb_frag_expand(int(which), _ip(out))
     return side, out[:side * side].reshape(side, side)
@@ -76,7 +75,6 @@ def test_bad_table_index():
 @pytest.mark.parametrize("log2n", [2, 3, 4, 5])
 def test_quant_fast_equals_quant_level(log2n):
     lib = core_lib()
-    lib.tv_quant_levels.restype = None
     lim = (1 << 17) - 1
     assert lim >= 64548
     coef = np.arange(-lim, lim + 1, dtype=np.int32)

@@ -216,8 +216,6 @@ def enc():
     from thinvids_amd._native import core_lib
 
     lib = core_lib()
-    lib.tv_hevc_spec_table.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_int]
-    lib.tv_hevc_spec_table.restype = C.c_int
 
     def get(name):
         n = lib.tv_hevc_spec_table(name.encode(), None, 0)

@@ -1,7 +1,6 @@
 """File ingest of the node job (verdict r3 item 3): the native parallel reader
 (csrc/core/io.cpp) and the GPU y4m staging path (ops/stage.read_y4m_device), the claim-ahead
 prefetch in node_job, and the synthetic y4m writer the ingest bench uses."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -11,11 +10,8 @@ import pytest
 def _pread(path, off, n, threads):
     from thinvids_amd._native import core_lib
 
-    lib = core_lib()
-    lib.tv_pread_parallel.argtypes = [C.c_char_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int]
-    lib.tv_pread_parallel.restype = C.c_longlong
     buf = np.zeros(n, np.uint8)
-    got = lib.tv_pread_parallel(str(path).encode(), off, n, buf.ctypes.data, threads)
+    got = core_lib().tv_pread_parallel(str(path).encode(), off, n, buf.ctypes.data, threads)
     return got, buf
 
 

@@ -53,7 +53,6 @@ def _native_rate(dx, dy):
     dx = np.ascontiguousarray(dx, np.int32)
     dy = np.ascontiguousarray(dy, np.int32)
     est, idx = np.empty_like(dx), np.empty_like(dx)
-    lib.tv_mv_rate.restype = None
     lib.tv_mv_rate(_ip(dx), _ip(dy), int(dx.size), _ip(est), _ip(idx))
     return est, idx
 
@@ -62,7 +61,6 @@ def _native_comp_bits(d):
     lib = core_lib()
     d = np.ascontiguousarray(d, np.int32)
     out = np.empty_like(d)
-    lib.tv_av1_mv_comp_bits.restype = None
     lib.tv_av1_mv_comp_bits(_ip(d), int(d.size), _ip(out))
     return out
 

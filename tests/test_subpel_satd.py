@@ -120,8 +120,6 @@ def _satd_blocks():
 
 def test_satd8x8_equals_numpy():
     f = core_lib().tv_satd8x8
-    f.restype = C.c_int
-    f.argtypes = [C.POINTER(C.c_int), C.c_int]
     H = _h8()
     for d in _satd_blocks():
         z = H @ d @ H

@@ -13,14 +13,14 @@ from pathlib import Path
 
 import numpy as np
 
+from . import _abi
+
 LIBDIR = Path(__file__).resolve().parent / "_lib"
 _lock = threading.Lock()
 _core = None
 _gpu = None
+_ptr_types: dict = {}  # numpy dtype -> ctypes pointer type, for ptr()
 
-u8p = C.POINTER(C.c_uint8)
-i16p = C.POINTER(C.c_int16)
-vp = C.c_void_p
 
 
 def _which(name: str) -> str:
@@ -60,9 +60,7 @@ def _ensure_built(name: str) -> Path:
 
 
 def build_hash(lib, which: str) -> str:
-    f = getattr(lib, f"tv_{which}_build_hash")
-    f.restype = C.c_char_p
-    return f().decode()
+    return getattr(lib, f"tv_{which}_build_hash")().decode()
 
 
 def _sig(lib, name, res, args):
@@ -72,47 +70,34 @@ def _sig(lib, name, res, args):
     return f
 
 
+def _load(name: str, table: dict):
+    """dlopen `name` and declare every function of `table` (a missing symbol fails the load)."""
+    lib = C.CDLL(str(_ensure_built(name)), mode=C.RTLD_GLOBAL)
+    for fn, (res, args) in table.items():
+        _sig(lib, fn, res, args)
+    return lib
+
+
 def core_lib():
     global _core
-    with _lock:
-        if _core is None:
-            lib = C.CDLL(str(_ensure_built("libtvcore.so")), mode=C.RTLD_GLOBAL)
-            _sig(lib, "tv_last_error", C.c_char_p, [])
-            _sig(lib, "tv_bytes_new", vp, [])
-            _sig(lib, "tv_bytes_free", None, [vp])
-            _sig(lib, "tv_bytes_size", C.c_size_t, [vp])
-            _sig(lib, "tv_bytes_data", vp, [vp])
-            _sig(lib, "tv_bytes_clear", None, [vp])
-            _sig(lib, "tv_synth_frame", None, [C.c_uint32, C.c_int, C.c_int, C.c_int, u8p, u8p, u8p])
-            _sig(lib, "tv_cpu_encoder_new", vp, [C.c_int] * 6)
-            _sig(lib, "tv_cpu_encoder_free", None, [vp])
-            _sig(lib, "tv_cpu_encoder_encode", C.c_int,
-                 [vp, u8p, u8p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, vp])
-            _sig(lib, "tv_cpu_encoder_recon", None, [vp, u8p, u8p, u8p])
-            _sig(lib, "tv_cpu_encoder_decisions", None, [vp, u8p, u8p, u8p, i16p, u8p])
-            _sig(lib, "tv_reconstruct_frame", C.c_int,
-                 [C.c_int] * 4 + [u8p] * 6 + [u8p, u8p, u8p, i16p, u8p, i16p, i16p, i16p, u8p, u8p, u8p])
-            _sig(lib, "tv_write_frame", C.c_int,
-                 [C.c_int] * 7 + [u8p, u8p, u8p, i16p, u8p, i16p, i16p, i16p, vp])
-            _sig(lib, "tv_decoder_new", vp, [])
-            _sig(lib, "tv_decoder_free", None, [vp])
-            _sig(lib, "tv_decoder_decode", C.c_int, [vp, u8p, C.c_size_t])
-            _sig(lib, "tv_decoder_info", None, [vp] + [C.POINTER(C.c_int)] * 5)
-            _sig(lib, "tv_decoder_frame", C.c_int, [vp, C.c_int, C.c_int, u8p, u8p, u8p])
-            _sig(lib, "tv_mux_mp4", C.c_int, [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp])
-            _sig(lib, "tv_demux_mp4", C.c_int,
-                 [u8p, C.c_size_t] + [C.POINTER(C.c_int)] * 5 + [vp])
-            _core = lib
+    if _core is None:
+        with _lock:
+            if _core is None:
+                lib = _load("libtvcore.so", _abi.CORE)
+                if lib.tv_side_track_size() != C.sizeof(_abi.SideTrack):
+                    raise RuntimeError("SideTrack layout mismatch between Python and libtvcore")
+                _core = lib
     return _core
 
 
 def check(rc: int) -> None:
-    if rc != 0:
-        raise RuntimeError(core_lib().tv_last_error().decode())
+    ok(rc, core_lib(), "tv_last_error")
 
 
-def ptr(a: np.ndarray, t=u8p):
+def ptr(a: np.ndarray):
+    """Typed pointer to a host array, by its dtype: the table's argtype then refuses an array of another type."""
     assert a.flags["C_CONTIGUOUS"], "array must be C-contiguous"
+    t = _ptr_types.get(a.dtype) or _ptr_types.setdefault(a.dtype, C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
     return a.ctypes.data_as(t)
 
 
@@ -141,8 +126,27 @@ class Bytes:
 def gpu_lib():
     """Load libtvgpu.so (HIP kernels + GPU engine).  Raises if it cannot be loaded."""
     global _gpu
-    core_lib()
-    with _lock:
-        if _gpu is None:
-            _gpu = C.CDLL(str(_ensure_built("libtvgpu.so")), mode=C.RTLD_GLOBAL)
+    if _gpu is None:
+        core_lib()
+        with _lock:
+            if _gpu is None:
+                _gpu = _load("libtvgpu.so", _abi.GPU)
     return _gpu
+
+
+def dptr(t) -> int:
+    """Device address of a torch tensor, for a `c_void_p` parameter."""
+    return t.data_ptr()
+
+
+def stream(device) -> int:
+    """Handle of torch's current stream on `device`, for a `c_void_p` stream parameter."""
+    import torch
+
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def ok(rc: int, lib, last_error: str, exc=RuntimeError) -> None:
+    """Raise `exc` with the message of `lib.<last_error>()` (a `tv_*_last_error`) if rc != 0."""
+    if rc != 0:
+        raise exc(getattr(lib, last_error)().decode())

@@ -22,10 +22,10 @@ range parallelism) and bitstreams are gathered over RCCL (``bench.py 
 """
 from __future__ import annotations
 
-import ctypes as C
 import threading
 from functools import lru_cache
 
+from .._native import gpu_lib, ok, stream
 from ..worker.helpers import output_geometry
 from .gpu_engine import GpuEngine, default_threads
 from .hevc import coded_size
@@ -98,24 +98,8 @@ def resize2d_plan(sw: int, sh: int, dw: int, dh: int, pw: int, ph: int, a: int =
     return 0, 0, 0
 
 
-def _ops():
-    from .._native import gpu_lib
-
-    lib = gpu_lib()
-    if not getattr(lib, "_abr_sigs", False):
-        vp, ci, cl = C.c_void_p, C.c_int, C.c_long
-        lib.tv_synth_p010.argtypes = [vp, vp, ci, ci, ci, ci, C.c_uint32, vp]
-        lib.tv_tonemap_pq_batch.argtypes = [vp, vp, ci, ci, ci, vp, C.c_float, C.c_float, vp]
-        lib.tv_resize_batch.argtypes = [vp, ci, ci, ci, cl, vp, ci, ci, ci, cl, ci, ci, ci,
-                                        vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, vp]
-        lib.tv_ops_last_error.restype = C.c_char_p
-        lib._abr_sigs = True
-    return lib
-
-
 def _ok(lib, rc: int) -> None:
-    if rc != 0:
-        raise RuntimeError(lib.tv_ops_last_error().decode())
+    ok(rc, lib, "tv_ops_last_error")
 
 
 class AbrLadder:
@@ -155,7 +139,7 @@ class AbrLadder:
         self.sdr = torch.empty((gop, self.src_fsz), dtype=u8, device=self.dev)
         self.tmp = torch.empty(gop * src_h * max(w for w, _ in self.rungs) if not fused else 1, dtype=i16,
                                device=self.dev)
-        self.lib = _ops()
+        self.lib = gpu_lib()
 
     def close(self) -> None:
         for e in self.engines:
@@ -163,10 +147,8 @@ class AbrLadder:
         self.engines = []
 
     # ------------------------------------------------------------ pre-processing
-    def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+    def _stream(self) -> int:
+        return stream(self.dev)
 
     def synth_p010(self, t0: int, n: int) -> None:
         """Seeded synthetic HDR10 frames t0..t0+n-1 into the chunk buffers."""
@@ -182,7 +164,7 @@ class AbrLadder:
         lib, st = self.lib, self._stream()
         staging = self.staging_slots[slot]
         _ok(lib, lib.tv_tonemap_pq_batch(self.y16.data_ptr(), self.uv16.data_ptr(), self.src_w, self.src_h, n,
-                                         self.sdr.data_ptr(), C.c_float(self.src_peak), C.c_float(self.dst_peak), st))
+                                         self.sdr.data_ptr(), self.src_peak, self.dst_peak, st))
         sw, sh = self.src_w, self.src_h
         full = (self.sdr.data_ptr(), self.src_fsz,
                 [(0, sw, sh, sw), (sw * sh, sw // 2, sh // 2, sw // 2), (sw * sh * 5 // 4, sw // 2, sh // 2, sw // 2)])

@@ -21,15 +21,13 @@ bit-exactly with dav1d (tests/test_av1_conformance.py), and with the decoder ora
 from __future__ import annotations
 
 import concurrent.futures as cf
-import ctypes as C
 import os
 from dataclasses import dataclass
 
 import numpy as np
 
+from .._native import dptr as _p, gpu_lib as _gpu, ok, stream
 from . import av1 as av1m
-
-_vp = C.c_void_p
 
 
 def _cdef_mask(pri, sec) -> int:
@@ -41,26 +39,8 @@ CDEF_MASK_Y = _cdef_mask((0, 1, 2, 3, 5, 7, 10, 13), (0, 2))
 CDEF_MASK_UV = _cdef_mask((0, 2, 4, 7), (0, 2))
 
 
-def _gpu():
-    from .._native import gpu_lib
-
-    lib = gpu_lib()
-    if not getattr(lib, "_av1e_sigs", False):
-        for n in ("tv_av1e_inter", "tv_av1e_intra", "tv_av1e_lfinfo", "tv_av1e_cdef_choose", "tv_av1e_lr_solve",
-                  "tv_av1e_unit_sse", "tv_av1e_merge", "tv_av1e_tb_len", "tv_av1e_tb_pack", "tv_av1e_cdef_skip"):
-            getattr(lib, n).restype = C.c_int
-        lib.tv_av1e_last_error.restype = C.c_char_p
-        lib._av1e_sigs = True
-    return lib
-
-
 def _ok(rc: int):
-    if rc != 0:
-        raise RuntimeError(_gpu().tv_av1e_last_error().decode())
-
-
-def _p(t):
-    return _vp(t.data_ptr())
+    ok(rc, _gpu(), "tv_av1e_last_error")
 
 
 LR_SETS = (4, 10)  # av1_enc.h lr_set()
@@ -173,7 +153,7 @@ class Av1GpuEngine:
 
         torch = self.torch
         lib = _gpu()
-        st = _vp(torch.cuda.current_stream(self.dev).cuda_stream)
+        st = stream(self.dev)
         W, H, B, q = self.W, self.H, nseg, self.q
         sy, su, sv = (x[:B] for x in self.src)
         ry, ru, rv = (x[:B] for x in self.rec)
@@ -232,7 +212,7 @@ class Av1GpuEngine:
         B, h, w = a.shape
         out = torch.empty((B, (-(-h // 64)) * (-(-w // 64))), dtype=torch.int64, device=self.dev)
         _ok(_gpu().tv_av1e_unit_sse(_p(a), _p(b), w, h, w if vw is None else vw, h if vh is None else vh, B, _p(out),
-                                    _vp(torch.cuda.current_stream(self.dev).cuda_stream)))
+                                    stream(self.dev)))
         return out
 
     def _restore(self, t: int, B: int, rate, dbk):
@@ -243,7 +223,7 @@ class Av1GpuEngine:
         from ..ops import av1 as ops
 
         torch = self.torch
-        st = _vp(torch.cuda.current_stream(self.dev).cuda_stream)
+        st = stream(self.dev)
         rate = rate.to(torch.int64).contiguous()
         out = []
         for p, (S, X, D) in enumerate(zip((x[:B] for x in self.src), self.fin, dbk)):
@@ -251,10 +231,8 @@ class Av1GpuEngine:
             nu = lr_grid(w) * lr_grid(h)
             prm = torch.empty((B, nu, 3), dtype=torch.int32, device=self.dev)
             o = torch.empty_like(X)
-            rc = ops._gpu().tv_gpu_sgr_select(_p(S), _p(X), _p(D), w, h, 1 if p else 0, B, _p(rate), _p(prm),
-                                              _p(o), st)
-            if rc != 0:
-                raise RuntimeError(ops._gpu().tv_av1_gpu_last_error().decode())
+            ok(_gpu().tv_gpu_sgr_select(_p(S), _p(X), _p(D), w, h, 1 if p else 0, B, _p(rate), _p(prm), _p(o), st),
+               _gpu(), "tv_av1_gpu_last_error")
             self.g_lr[t, :B, p, :nu] = prm
             out.append(o)
         return tuple(out)
@@ -313,19 +291,18 @@ class Av1GpuEngine:
         ntb = F * nseg * nb
         with torch.cuda.stream(cs):
             cs.wait_event(ev)
-            st = _vp(cs.cuda_stream)
+            st = cs.cuda_stream
             lens, ends = [], []
             for p, k in enumerate(("ly", "lu", "lv")):
                 ln = torch.empty(ntb, dtype=torch.int32, device=self.dev)
-                _ok(lib.tv_av1e_tb_len(_p(S[k]), _p(S["mode"]), C.c_long(ntb), nb, nseg, Bmax, p, _p(ln), st))
+                _ok(lib.tv_av1e_tb_len(_p(S[k]), _p(S["mode"]), ntb, nb, nseg, Bmax, p, _p(ln), st))
                 lens.append(ln)
                 ends.append(torch.cumsum(ln, 0, dtype=torch.int64))
             totals = torch.stack([e[-1] for e in ends]).cpu().tolist()
             outs = []
             for p, k in enumerate(("ly", "lu", "lv")):
                 o = torch.empty(max(1, totals[p]), dtype=torch.int16, device=self.dev)
-                _ok(lib.tv_av1e_tb_pack(_p(S[k]), _p(lens[p]), _p(ends[p]), C.c_long(ntb), nb, nseg, Bmax, p, _p(o),
-                                        st))
+                _ok(lib.tv_av1e_tb_pack(_p(S[k]), _p(lens[p]), _p(ends[p]), ntb, nb, nseg, Bmax, p, _p(o), st))
                 outs.append((o, (ends[p] - lens[p]).view(F, nseg, nb)[:, :, 0]))
             host = GopHost(
                 nframes=F,

@@ -8,43 +8,12 @@ import os
 
 import numpy as np
 
-from .._native import gpu_lib, ptr
+from .._native import gpu_lib, ok, ptr
 from .hevc import coded_size
-
-_sigs_done = False
-
-
-def _lib():
-    global _sigs_done
-    lib = gpu_lib()
-    if not _sigs_done:
-        vp = C.c_void_p
-        lib.tv_gpu_last_error.restype = C.c_char_p
-        lib.tv_gpu_device_count.restype = C.c_int
-        lib.tv_engine_new.restype = vp
-        lib.tv_engine_new.argtypes = [C.c_int] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]
-        lib.tv_engine_new_b.restype = vp
-        lib.tv_engine_new_b.argtypes = [C.c_int] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-        lib.tv_engine_free.argtypes = [vp]
-        lib.tv_engine_encode_synth.restype = C.c_int
-        lib.tv_engine_encode_synth.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.c_int, vp]
-        lib.tv_engine_encode_host.restype = C.c_int
-        lib.tv_engine_encode_host.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, vp]
-        lib.tv_engine_encode_device.restype = C.c_int
-        lib.tv_engine_encode_device.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-        lib.tv_engine_segment_size.restype = C.c_size_t
-        lib.tv_engine_segment_size.argtypes = [vp, C.c_int]
-        lib.tv_engine_segment_copy.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8)]
-        lib.tv_engine_sse.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
-        lib.tv_engine_timing.argtypes = [vp] + [C.POINTER(C.c_double)] * 4
-        lib.tv_engine_last_recon.restype = C.c_int
-        lib.tv_engine_last_recon.argtypes = [vp, C.c_int] + [C.POINTER(C.c_uint8)] * 3
-        _sigs_done = True
-    return lib
 
 
 def device_count() -> int:
-    return _lib().tv_gpu_device_count()
+    return gpu_lib().tv_gpu_device_count()
 
 
 def cgroup_cpu_quota() -> float | None:
@@ -99,7 +68,7 @@ class GpuEngine:
         (default; env TV_ENTROPY) picks by the host CPU budget (:func:`auto_entropy`).
         wpp=False always codes on the host.  `subpel_satd` (off by default): half- / quarter-pel
         vectors chosen by Hadamard SATD + MV rate (tv/me_model.h; k_inter_me<true>)."""
-        self.lib = _lib()
+        self.lib = gpu_lib()
         self.width, self.height, self.qp = width, height, qp
         self.batch, self.gop = batch, gop
         self.cw, self.ch = coded_size(width, height)
@@ -134,11 +103,10 @@ class GpuEngine:
             raise ValueError(f"qp map must be [{nseg}][{nframes}] in 0..51")
         self._qbuf = np.ascontiguousarray(q, dtype=np.int8)
         self.last_qp = self._qbuf
-        return C.c_void_p(self._qbuf.ctypes.data)
+        return self._qbuf.ctypes.data
 
     def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self.lib.tv_gpu_last_error().decode())
+        ok(rc, self.lib, "tv_gpu_last_error")
 
     def encode_synthetic(self, starts, nframes: int | None = None, qp=None) -> list[bytes]:
         """Encode len(starts) segments generated on the GPU; segment b = synthetic frames
@@ -182,7 +150,7 @@ class GpuEngine:
             raise ValueError(f"need 1..{self.batch} segments of 1..{self.gop} frames")
         if not frames.is_cuda or not frames.is_contiguous() or frames.numel() * frames.element_size() < nseg * nframes * fsz:
             raise ValueError("frames must be a contiguous CUDA tensor of nseg*nframes coded-size I420 frames")
-        self._check(self.lib.tv_engine_encode_device(self.h, C.c_void_p(frames.data_ptr()), nseg, nframes,
+        self._check(self.lib.tv_engine_encode_device(self.h, frames.data_ptr(), nseg, nframes,
                                                      self._qmap(qp, nseg, nframes)))
         self.last_frames = nframes
         return [self.segment(b) for b in range(nseg)]
@@ -196,7 +164,6 @@ class GpuEngine:
     def footprint(self) -> dict:
         """HBM and pinned-host bytes this engine allocated (the native allocation ledger)."""
         d, h = C.c_ulonglong(), C.c_ulonglong()
-        self.lib.tv_engine_footprint.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         self.lib.tv_engine_footprint(self.h, C.byref(d), C.byref(h))
         return {"dev": int(d.value), "host": int(h.value)}
 
@@ -223,15 +190,10 @@ class GpuEngine:
         """GPU entropy coding: whether it is on, pictures the host writer coded instead since
         construction (device capacity), and the OR of their device status words."""
         on, fb, st = C.c_int(), C.c_longlong(), C.c_int()
-        f = self.lib.tv_engine_entropy_stats
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
-        f(self.h, C.byref(on), C.byref(fb), C.byref(st))
-        hp = self.lib.tv_engine_entropy_host_pictures
-        hp.argtypes, hp.restype = [C.c_void_p], C.c_longlong
-        lp = self.lib.tv_engine_entropy_lane_pictures
-        lp.argtypes, lp.restype = [C.c_void_p, C.c_int], C.c_longlong
+        self.lib.tv_engine_entropy_stats(self.h, C.byref(on), C.byref(fb), C.byref(st))
         return {"gpu": bool(on.value), "fallbacks": int(fb.value), "status": int(st.value),
-                "host_pictures": int(hp(self.h)), "lane_pictures": [int(lp(self.h, l)) for l in range(2)]}
+                "host_pictures": self.lib.tv_engine_entropy_host_pictures(self.h),
+                "lane_pictures": [self.lib.tv_engine_entropy_lane_pictures(self.h, l) for l in range(2)]}
 
     def last_recon(self, b: int):
         y = np.empty((self.ch, self.cw), np.uint8)
@@ -277,12 +239,10 @@ def estimate_footprint(width: int, height: int, batch: int, gop: int, sao: bool 
     native constructor's own size formulas without allocating (tv_engine_estimate)."""
     from .hevc import codec_flags
 
-    lib = _lib()
+    lib = gpu_lib()
     ent = resolve_entropy(entropy) if wpp else "host"
     flags = codec_flags(True, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd) | (32 if ent == "host" else 0)
     d, h = C.c_ulonglong(), C.c_ulonglong()
-    f = lib.tv_engine_estimate
-    f.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_ulonglong)] * 2
-    if f(width, height, batch, gop, flags, int(bframes), C.byref(d), C.byref(h)) != 0:
-        raise ValueError(lib.tv_gpu_last_error().decode())
+    ok(lib.tv_engine_estimate(width, height, batch, gop, flags, int(bframes), C.byref(d), C.byref(h)),
+       lib, "tv_gpu_last_error", ValueError)
     return {"dev": int(d.value), "host": int(h.value)}

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .._native import u8p, Bytes, check, core_lib, i16p, ptr
+from .._native import Bytes, check, core_lib, ok, ptr
 
 Frame = tuple  # (Y, U, V)
 
@@ -78,23 +78,15 @@ class CpuEncoder:
         self.width, self.height, self.qp = width, height, qp
         self.cw, self.ch = coded_size(width, height)
         self.bframes = int(bframes)
+        flags = codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd)
         if self.bframes > 1:
             if crf:
                 raise ValueError("CRF with B frames is not supported by the golden encoder")
-            f = self.lib.tv_cpu_encoder_new_b
-            f.restype = C.c_void_p
-            f.argtypes = [C.c_int] * 7
-            self.h = f(width, height, qp, codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd), search_range, max_merge,
-                       self.bframes)
+            self.h = self.lib.tv_cpu_encoder_new_b(width, height, qp, flags, search_range, max_merge, self.bframes)
         elif crf:
-            f = self.lib.tv_cpu_encoder_new_crf
-            f.restype = C.c_void_p
-            f.argtypes = [C.c_int] * 7
-            self.h = f(width, height, qp, codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd), search_range, max_merge,
-                       int(crf))
+            self.h = self.lib.tv_cpu_encoder_new_crf(width, height, qp, flags, search_range, max_merge, int(crf))
         else:
-            self.h = self.lib.tv_cpu_encoder_new(width, height, qp, codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd),
-                                                 search_range, max_merge)
+            self.h = self.lib.tv_cpu_encoder_new(width, height, qp, flags, search_range, max_merge)
         if not self.h:
             raise ValueError(self.lib.tv_last_error().decode())
         self.out = Bytes()
@@ -108,10 +100,7 @@ class CpuEncoder:
         """Hierarchical-B mode: plan the next segment; returns the display index of every
         picture in coding order (feed the frames to :meth:`encode` in that order)."""
         disp = (C.c_int * nframes)()
-        f = self.lib.tv_cpu_encoder_begin_gop
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        check(f(self.h, nframes, disp))
+        check(self.lib.tv_cpu_encoder_begin_gop(self.h, nframes, disp))
         return list(disp)
 
     def encode(self, frame: Frame, idr: bool, poc: int, qp: int | None = None) -> bytes:
@@ -122,10 +111,8 @@ class CpuEncoder:
             check(self.lib.tv_cpu_encoder_encode(self.h, ptr(y), ptr(u), ptr(v), y.shape[1], u.shape[1],
                                                  int(idr), poc, self.out.h))
         else:
-            f = self.lib.tv_cpu_encoder_encode_qp
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, u8p, u8p, u8p] + [C.c_int] * 5 + [C.c_void_p]
-            check(f(self.h, ptr(y), ptr(u), ptr(v), y.shape[1], u.shape[1], int(idr), poc, int(qp), self.out.h))
+            check(self.lib.tv_cpu_encoder_encode_qp(self.h, ptr(y), ptr(u), ptr(v), y.shape[1], u.shape[1], int(idr),
+                                                    poc, int(qp), self.out.h))
         return self.out.tobytes()
 
     def recon(self) -> Frame:
@@ -139,8 +126,8 @@ class CpuEncoder:
         w8, h8 = self.cw // 8, self.ch // 8
         d = {k: np.empty((h8, w8), np.uint8) for k in ("cu_log2", "intra", "ipm", "cbf")}
         mv = np.empty((h8, w8, 2), np.int16)
-        self.lib.tv_cpu_encoder_decisions(self.h, ptr(d["cu_log2"]), ptr(d["intra"]), ptr(d["ipm"]),
-                                          ptr(mv, i16p), ptr(d["cbf"]))
+        self.lib.tv_cpu_encoder_decisions(self.h, ptr(d["cu_log2"]), ptr(d["intra"]), ptr(d["ipm"]), ptr(mv),
+                                          ptr(d["cbf"]))
         d["mv"] = mv
         return d
 
@@ -151,10 +138,7 @@ def gop_plan(nframes: int, bframes: int) -> dict:
     lib = core_lib()
     arrs = [(C.c_int * max(1, nframes))() for _ in range(5)]
     info = (C.c_int * 2)()
-    f = lib.tv_gop_plan
-    f.restype = C.c_int
-    f.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 6
-    n = f(nframes, bframes, *arrs, info)
+    n = lib.tv_gop_plan(nframes, bframes, *arrs, info)
     keys = ("disp", "type", "ref0", "ref1", "layer")
     out = {k: list(a)[:n] for k, a in zip(keys, arrs)}
     out["dpb_size"], out["num_reorder"] = info[0], info[1]
@@ -197,10 +181,7 @@ def display_offsets(annexb: bytes) -> np.ndarray:
     buf = np.frombuffer(annexb, np.uint8)
     cap = max(1, annexb.count(b"\x00\x00\x01"))
     out = np.zeros(cap, np.int32)
-    f = lib.tv_hevc_display_offsets
-    f.restype = C.c_int
-    f.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int), C.c_int]
-    n = f(buf.ctypes.data_as(C.POINTER(C.c_uint8)), len(buf), out.ctypes.data_as(C.POINTER(C.c_int)), cap)
+    n = lib.tv_hevc_display_offsets(ptr(buf), len(buf), ptr(out), cap)
     if n < 0:
         raise ValueError(lib.tv_last_error().decode())
     return out[:n]
@@ -219,12 +200,6 @@ class DecodedStream:
 def probe_annexb(annexb: bytes) -> dict:
     """Header-only probe (SPS geometry, picture and IDR counts): nothing is decoded."""
     lib = core_lib()
-    if not getattr(lib, "_probe_sig", False):
-        lib.tv_hevc_probe.argtypes = [C.POINTER(C.c_uint8), C.c_size_t] + [C.POINTER(C.c_int)] * 4
-        lib.tv_hevc_probe.restype = C.c_int
-        lib.tv_decoder_decode_range.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.c_int]
-        lib.tv_decoder_decode_range.restype = C.c_int
-        lib._probe_sig = True
     buf = np.frombuffer(annexb, np.uint8)
     w, h, n, k = (C.c_int() for _ in range(4))
     check(lib.tv_hevc_probe(ptr(buf), len(annexb), C.byref(w), C.byref(h), C.byref(n), C.byref(k)))
@@ -235,7 +210,6 @@ def decode(annexb: bytes, coded: bool = True, first: int = 0, count: int = -1) -
     """Decode an Annex-B HEVC stream with the native decoder oracle; `first`/`count` decode
     only that picture range (from the nearest preceding IDR)."""
     lib = core_lib()
-    probe_annexb(b"")  # signatures
     h = lib.tv_decoder_new()
     try:
         buf = np.frombuffer(annexb, np.uint8)
@@ -267,9 +241,9 @@ def write_frame(width: int, height: int, qp: int, idr: bool, poc: int, dec: dict
     check(lib.tv_write_frame(width, height, qp, int(deblock), max_merge, int(idr), poc,
                              ptr(np.ascontiguousarray(dec["cu_log2"])), ptr(np.ascontiguousarray(dec["intra"])),
                              ptr(np.ascontiguousarray(dec["ipm"])),
-                             ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16), i16p),
-                             ptr(np.ascontiguousarray(dec["cbf"])), ptr(cy, i16p), ptr(cu, i16p),
-                             ptr(cv, i16p), out.h))
+                             ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16)),
+                             ptr(np.ascontiguousarray(dec["cbf"])), ptr(cy), ptr(cu),
+                             ptr(cv), out.h))
     return out.tobytes()
 
 
@@ -292,8 +266,8 @@ def reconstruct_reference(width: int, height: int, qp: int, src: Frame, ref: Fra
         width, height, qp, int(deblock), ptr(s[0]), ptr(s[1]), ptr(s[2]),
         ptr(r[0]) if r else null, ptr(r[1]) if r else null, ptr(r[2]) if r else null,
         ptr(np.ascontiguousarray(dec["cu_log2"])), ptr(np.ascontiguousarray(dec["intra"])),
-        ptr(np.ascontiguousarray(dec["ipm"])), ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16), i16p),
-        ptr(cbf), ptr(cy, i16p), ptr(cu, i16p), ptr(cv, i16p), ptr(ry), ptr(ru), ptr(rv)))
+        ptr(np.ascontiguousarray(dec["ipm"])), ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16)),
+        ptr(cbf), ptr(cy), ptr(cu), ptr(cv), ptr(ry), ptr(ru), ptr(rv)))
     return cbf, (cy, cu, cv), (ry, ru, rv)
 
 
@@ -309,11 +283,6 @@ def mux_mp4_file(segments, width: int, height: int, fps_num: int, fps_den: int, 
     """Write the concatenation of Annex-B segments as a faststart MP4 at `path`, streaming
     the payload from the segment buffers (no joined copy).  Returns the file size."""
     lib = core_lib()
-    if not getattr(lib, "_muxf_sig", False):
-        lib.tv_mux_mp4_file.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_ulonglong)]
-        lib.tv_mux_mp4_file.restype = C.c_int
-        lib._muxf_sig = True
     segs = [s for s in segments if len(s)]
     keep = [np.frombuffer(s, np.uint8) for s in segs]
     ptrs = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
@@ -332,16 +301,6 @@ class Mp4StreamWriter:
 
     def __init__(self, path: str, width: int, height: int, fps_num: int, fps_den: int, max_samples: int):
         lib = core_lib()
-        if not getattr(lib, "_mp4s_sig", False):
-            lib.tv_mp4s_open.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong]
-            lib.tv_mp4s_open.restype = C.c_void_p
-            lib.tv_mp4s_append.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-            lib.tv_mp4s_append.restype = C.c_int
-            lib.tv_mp4s_close.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
-            lib.tv_mp4s_close.restype = C.c_int
-            lib.tv_mp4s_abort.argtypes = [C.c_void_p]
-            lib.tv_mp4s_last_error.restype = C.c_char_p
-            lib._mp4s_sig = True
         self.lib, self.path = lib, path
         self.h = lib.tv_mp4s_open(path.encode(), width, height, fps_num, fps_den, max(1, int(max_samples)))
         if not self.h:
@@ -358,8 +317,7 @@ class Mp4StreamWriter:
         with self.lock:
             if not self.h:
                 raise RuntimeError("stream writer closed")
-            if self.lib.tv_mp4s_append(self.h, buf.ctypes.data, len(buf)) != 0:
-                raise RuntimeError(self.lib.tv_mp4s_last_error().decode())
+            ok(self.lib.tv_mp4s_append(self.h, ptr(buf), len(buf)), self.lib, "tv_mp4s_last_error")
         self.payload += len(buf)
 
     def close(self) -> int:
@@ -369,8 +327,7 @@ class Mp4StreamWriter:
             if not h:
                 raise RuntimeError("stream writer closed")
             out = C.c_ulonglong()
-            if self.lib.tv_mp4s_close(h, C.byref(out)) != 0:
-                raise RuntimeError(self.lib.tv_mp4s_last_error().decode())
+            ok(self.lib.tv_mp4s_close(h, C.byref(out)), self.lib, "tv_mp4s_last_error")
         return int(out.value)
 
     def abort(self) -> None:

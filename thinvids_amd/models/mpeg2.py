@@ -15,7 +15,6 @@ decoder exists in this image); the inverse DCT is the 13818-2 Annex A definition
 """
 from __future__ import annotations
 
-import ctypes as C
 import mmap
 import os
 import struct
@@ -23,28 +22,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from .._native import Bytes, core_lib, ptr, u8p
-
-i32p = C.POINTER(C.c_int32)
-i64p = C.POINTER(C.c_int64)
+from .._native import Bytes, core_lib as _lib, ptr
 
 ES_EXTS = (".m2v", ".mpv", ".m2video")
-
-
-def _lib():
-    lib = core_lib()
-    if not getattr(lib, "_mpeg2_sigs", False):
-        lib.tv_mpeg2_last_error.restype = C.c_char_p
-        lib.tv_mpeg2_encode.argtypes = [i32p, C.c_int, C.c_int, u8p, C.c_void_p, i64p, i32p, u8p]
-        lib.tv_mpeg2_probe.argtypes = [u8p, C.c_size_t, i32p]
-        lib.tv_mpeg2_raps.argtypes = [u8p, C.c_size_t, i64p, i64p, i32p, i32p, C.c_int]
-        lib.tv_mpeg2_decode.argtypes = [u8p, C.c_size_t, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, u8p,
-                                        i32p, i64p]
-        lib.tv_mpeg2_stat_name.restype = C.c_char_p
-        lib.tv_mpeg2_stat_name.argtypes = [C.c_int]
-        lib.tv_mpeg2_table.argtypes = [C.c_int, i32p, i32p, i32p, C.c_int]
-        lib._mpeg2_sigs = True
-    return lib
 
 
 def _check(rc: int) -> int:
@@ -79,8 +59,7 @@ def encode(frames, **cfg):
     sizes = np.zeros(n, np.int64)
     disp = np.zeros(n, np.int32)
     rec = np.zeros(n * w * h * 3 // 2, np.uint8)
-    _check(_lib().tv_mpeg2_encode(ptr(arr, i32p), len(arr), n, ptr(yuv), out.h, ptr(sizes, i64p), ptr(disp, i32p),
-                                  ptr(rec)))
+    _check(_lib().tv_mpeg2_encode(ptr(arr), len(arr), n, ptr(yuv), out.h, ptr(sizes), ptr(disp), ptr(rec)))
     es = out.tobytes()
     units, o = [], 0
     for s in sizes:
@@ -104,7 +83,7 @@ def _split(buf: np.ndarray, n: int, w: int, h: int):
 def probe_es(data) -> dict:
     a, n = _buf(data)
     info = np.zeros(16, np.int32)
-    _check(_lib().tv_mpeg2_probe(ptr(a), n, ptr(info, i32p)))
+    _check(_lib().tv_mpeg2_probe(ptr(a), n, ptr(info)))
     keys = ("width", "height", "frames", "fps_num", "fps_den", "interlaced", "top_field_first", "field_pictures",
             "progressive_sequence", "aspect", "profile_level", "raps", "mb_width", "mb_height", "mpeg2")
     return {k: int(v) for k, v in zip(keys, info)}
@@ -116,7 +95,7 @@ def raps(data) -> list[tuple[int, int, int, bool]]:
     cnt = _check(_lib().tv_mpeg2_raps(ptr(a), n, None, None, None, None, 0))
     off, so = np.zeros(cnt, np.int64), np.zeros(cnt, np.int64)
     fb, cl = np.zeros(cnt, np.int32), np.zeros(cnt, np.int32)
-    _check(_lib().tv_mpeg2_raps(ptr(a), n, ptr(off, i64p), ptr(so, i64p), ptr(fb, i32p), ptr(cl, i32p), cnt))
+    _check(_lib().tv_mpeg2_raps(ptr(a), n, ptr(off), ptr(so), ptr(fb), ptr(cl), cnt))
     return [(int(off[i]), int(so[i]), int(fb[i]), bool(cl[i])) for i in range(cnt)]
 
 
@@ -126,8 +105,7 @@ def _decode(a: np.ndarray, n: int, seq_off: int, start: int, base: int, first: i
     out = np.zeros(count * (w * h + 2 * cw * ch), np.uint8)
     got = np.zeros(count, np.int32)
     st = np.zeros(_lib().tv_mpeg2_num_stats(), np.int64)
-    _check(_lib().tv_mpeg2_decode(ptr(a), n, seq_off, start, base, first, count, ptr(out), ptr(got, i32p),
-                                  ptr(st, i64p)))
+    _check(_lib().tv_mpeg2_decode(ptr(a), n, seq_off, start, base, first, count, ptr(out), ptr(got), ptr(st)))
     if stats is not None:
         for i, v in enumerate(st):
             name = _lib().tv_mpeg2_stat_name(i).decode()
@@ -166,7 +144,7 @@ def table(which: int, writer: bool = False) -> list[tuple[str, int]]:
     w = which + (100 if writer else 0)
     n = _lib().tv_mpeg2_table(w, None, None, None, 0)
     code, ln, val = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
-    _lib().tv_mpeg2_table(w, ptr(code, i32p), ptr(ln, i32p), ptr(val, i32p), n)
+    _lib().tv_mpeg2_table(w, ptr(code), ptr(ln), ptr(val), n)
     if which >= 10:
         return [(str(int(c)), int(v)) for c, v in zip(code, val)]
     return [(format(int(c), f"0{int(l)}b"), int(v)) for c, l, v in zip(code, ln, val)]

@@ -716,34 +716,18 @@ def plan_output(src_path: str | None, audio_index: int | None = 0) -> OutputPlan
 
 
 # ------------------------------------------------------------------------- muxing
-class _CSide(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("codec", C.c_int32), ("timescale", C.c_int32), ("channels", C.c_int32),
-                ("sample_rate", C.c_int32), ("bits", C.c_int32), ("is_default", C.c_int32), ("reserved", C.c_int32),
-                ("lang", C.c_char * 4), ("mkv_codec_id", C.c_char_p), ("priv", C.c_void_p), ("priv_size", C.c_uint64),
-                ("path", C.c_char_p), ("data", C.c_void_p), ("nsamples", C.c_int64),
-                ("offsets", C.c_void_p), ("sizes", C.c_void_p), ("pts", C.c_void_p), ("durs", C.c_void_p)]
-
-
 def mux(segments, width: int, height: int, fps_num: int, fps_den: int, path: str,
         tracks: list[SideStream] = (), container: int = CONTAINER_MP4) -> int:
     """Write the Annex-B segments + side streams to `path` (native writer).  Returns bytes."""
-    from .hevc import check, core_lib
+    from .._abi import SideTrack
+    from .._native import check, core_lib
 
     lib = core_lib()
-    if not getattr(lib, "_muxfile_sig", False):
-        lib.tv_mux_file.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.POINTER(_CSide), C.c_int, C.c_int, C.c_char_p,
-                                    C.POINTER(C.c_ulonglong)]
-        lib.tv_mux_file.restype = C.c_int
-        lib.tv_side_track_size.restype = C.c_size_t
-        if lib.tv_side_track_size() != C.sizeof(_CSide):
-            raise RuntimeError("SideTrack layout mismatch between Python and libtvcore")
-        lib._muxfile_sig = True
     segs = [s for s in segments if len(s)]
     keep = [np.frombuffer(s, np.uint8) for s in segs]
     ptrs = (C.c_void_p * max(1, len(keep)))(*[k.ctypes.data for k in keep])
     sizes = (C.c_size_t * max(1, len(keep)))(*[len(k) for k in keep])
-    arr = (_CSide * max(1, len(tracks)))()
+    arr = (SideTrack * max(1, len(tracks)))()
     hold = []
     for i, s in enumerate(tracks):
         offs = np.ascontiguousarray(s.offsets, np.uint64)

@@ -16,17 +16,18 @@ the host from the kernels' statistics.
 Scope: the filters follow the AV1 arithmetic (8-bit: Cdef_Directions, primary/secondary
 taps and constrain(), variance-adjusted luma strength, 7-tap symmetric Wiener with
 InterRound0/1 = 3/11, SGR parameter sets and A/B guide); loop restoration works on 64x64
-units with edge-replicated context instead of AV1's 64-row stripes.  There is no AV1
-bitstream writer: a conformant one needs the spec's default CDF tables, which are not
-available offline (the range coder itself is in csrc/core/av1_tools.cpp).  Parity with
-libaom/dav1d is therefore unpinned; tests pin GPU == C++ golden and the filters' gains.
+units with edge-replicated context instead of AV1's 64-row stripes.  The bitstream writer
+is csrc/core/av1_codec.cpp (models/av1.py); tests/test_av1_conformance.py pins its streams,
+these filters included, against dav1d.  The tests of this module pin GPU == C++ golden and
+the filters' gains.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
+
+from .._native import core_lib as _core, dptr as _t, gpu_lib as _gpu, ok, ptr as _p, stream
 
 RU = 64  # restoration unit
 PRESETS = 64  # CDEF (primary 0..15) x (secondary {0,1,2,4})
@@ -35,64 +36,9 @@ WIENER_MAX = np.array([10, 8, 46])
 SGR_XQD_MIN = np.array([-96, -32])
 SGR_XQD_MAX = np.array([31, 95])
 
-_vp = C.c_void_p
-
-
-def _core():
-    from .._native import core_lib
-
-    lib = core_lib()
-    if not getattr(lib, "_av1_sigs", False):
-        i, u8, i32, i64 = C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        lib.tv_av1_cdef_find_dirs.argtypes = [u8, i, i, u8, i32]
-        lib.tv_av1_cdef_search.argtypes = [u8, u8, i, i, i, u8, i32, i, i, C.POINTER(C.c_uint64)]
-        lib.tv_av1_cdef_apply.argtypes = [u8, i, i, i, u8, i32, i, i, C.POINTER(C.c_int8), u8]
-        lib.tv_av1_wiener_apply.argtypes = [u8, i, i, i32, u8]
-        lib.tv_av1_wiener_stats.argtypes = [u8, u8, i, i, i, i32, i64]
-        lib.tv_av1_sgr_apply.argtypes = [u8, i, i, i32, u8]
-        lib.tv_av1_sgr_stats.argtypes = [u8, u8, i, i, i, i64]
-        lib.tv_av1_sgr_filter_planes.argtypes = [u8, i, i, i, i32, i32]
-        lib.tv_av1_deblock.argtypes = [u8, i, i, i, C.POINTER(C.c_uint32), i, u8]
-        lib.tv_av1_deblock.restype = C.c_int
-        lib.tv_av1_last_error.restype = C.c_char_p
-        lib.tv_av1_rc_roundtrip.argtypes = [_vp, _vp, _vp, i, i, i, _vp, _vp]
-        lib.tv_av1_rc_roundtrip.restype = C.c_int
-        lib._av1_sigs = True
-    return lib
-
-
-def _gpu():
-    from .._native import gpu_lib
-
-    lib = gpu_lib()
-    if not getattr(lib, "_av1_sigs", False):
-        for name in ("tv_gpu_cdef_dirs", "tv_gpu_cdef_search", "tv_gpu_cdef_apply", "tv_gpu_wiener_apply",
-                     "tv_gpu_wiener_stats", "tv_gpu_sgr_stats", "tv_gpu_sgr_apply", "tv_gpu_av1_deblock",
-                     "tv_gpu_sgr_select", "tv_gpu_av1_deblock_step"):
-            getattr(lib, name).restype = C.c_int
-        lib.tv_av1_gpu_last_error.restype = C.c_char_p
-        lib._av1_sigs = True
-    return lib
-
-
-def _p(a: np.ndarray, t=C.c_uint8):
-    assert a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-def _t(x):
-    return _vp(x.data_ptr())
-
-
-def _stream(x):
-    import torch
-
-    return _vp(torch.cuda.current_stream(x.device).cuda_stream)
-
 
 def _check(rc: int):
-    if rc != 0:
-        raise RuntimeError(_gpu().tv_av1_gpu_last_error().decode())
+    ok(rc, _gpu(), "tv_av1_gpu_last_error")
 
 
 def _is_np(x) -> bool:
@@ -116,7 +62,7 @@ def cdef_dirs(Y):
         h, w = Y.shape
         d = np.zeros((h // 8, w // 8), np.uint8)
         v = np.zeros((h // 8, w // 8), np.int32)
-        _core().tv_av1_cdef_find_dirs(_p(np.ascontiguousarray(Y)), w, h, _p(d), _p(v, C.c_int32))
+        _core().tv_av1_cdef_find_dirs(_p(np.ascontiguousarray(Y)), w, h, _p(d), _p(v))
         return d, v
     import torch
 
@@ -124,7 +70,7 @@ def cdef_dirs(Y):
     n8 = (h // 8) * (w // 8)
     d = torch.empty((B, n8), dtype=torch.uint8, device=Y.device)
     v = torch.empty((B, n8), dtype=torch.int32, device=Y.device)
-    _check(_gpu().tv_gpu_cdef_dirs(_t(Y.contiguous()), w, h, B, _t(d), _t(v), _stream(Y)))
+    _check(_gpu().tv_gpu_cdef_dirs(_t(Y.contiguous()), w, h, B, _t(d), _t(v), stream(Y.device)))
     return d, v
 
 
@@ -139,8 +85,7 @@ def cdef_search(src, rec, dirs, var, chroma: bool, damping: int = 5, luma_w8: in
         lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
         out = np.zeros((n_fb(w, h, chroma), PRESETS), np.uint64)
         _core().tv_av1_cdef_search(_p(np.ascontiguousarray(src)), _p(np.ascontiguousarray(rec)), w, h, int(chroma),
-                                   _p(np.ascontiguousarray(dirs)), _p(np.ascontiguousarray(var), C.c_int32), lw8,
-                                   damping, _p(out, C.c_uint64))
+                                   _p(np.ascontiguousarray(dirs)), _p(np.ascontiguousarray(var)), lw8, damping, _p(out))
         return out
     import torch
 
@@ -148,8 +93,8 @@ def cdef_search(src, rec, dirs, var, chroma: bool, damping: int = 5, luma_w8: in
     lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
     out = torch.empty((B, n_fb(w, h, chroma), PRESETS), dtype=torch.int64, device=rec.device)
     _check(_gpu().tv_gpu_cdef_search(_t(src.contiguous()), _t(rec.contiguous()), w, h, B, int(chroma),
-                                     _t(dirs), _t(var), lw8, dirs.shape[-1], damping, _t(out), _stream(rec),
-                                     C.c_ulonglong(pmask), int(checker)))
+                                     _t(dirs), _t(var), lw8, dirs.shape[-1], damping, _t(out), stream(rec.device),
+                                     pmask, int(checker)))
     return out
 
 
@@ -160,8 +105,8 @@ def cdef_apply(rec, dirs, var, fb_preset, chroma: bool, damping: int = 5, luma_w
         lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
         out = np.empty_like(rec)
         _core().tv_av1_cdef_apply(_p(np.ascontiguousarray(rec)), w, h, int(chroma), _p(np.ascontiguousarray(dirs)),
-                                  _p(np.ascontiguousarray(var), C.c_int32), lw8, damping,
-                                  _p(np.ascontiguousarray(fb_preset, np.int8), C.c_int8), _p(out))
+                                  _p(np.ascontiguousarray(var)), lw8, damping,
+                                  _p(np.ascontiguousarray(fb_preset, np.int8)), _p(out))
         return out
     import torch
 
@@ -170,7 +115,7 @@ def cdef_apply(rec, dirs, var, fb_preset, chroma: bool, damping: int = 5, luma_w
     out = torch.empty_like(rec)
     fbp = fb_preset.to(device=rec.device, dtype=torch.int8).contiguous()
     _check(_gpu().tv_gpu_cdef_apply(_t(rec.contiguous()), w, h, B, int(chroma), _t(dirs), _t(var), lw8,
-                                    dirs.shape[-1], damping, _t(fbp), _t(out), _stream(rec)))
+                                    dirs.shape[-1], damping, _t(fbp), _t(out), stream(rec.device)))
     return out
 
 
@@ -208,14 +153,14 @@ def wiener_apply(rec, coef):
         h, w = rec.shape
         out = np.empty_like(rec)
         _core().tv_av1_wiener_apply(_p(np.ascontiguousarray(rec)), w, h,
-                                    _p(np.ascontiguousarray(coef, np.int32), C.c_int32), _p(out))
+                                    _p(np.ascontiguousarray(coef, np.int32)), _p(out))
         return out
     import torch
 
     B, h, w = rec.shape
     out = torch.empty_like(rec)
     cf = torch.as_tensor(np.asarray(coef, np.int32)).to(rec.device).reshape(B, -1, 6).contiguous()
-    _check(_gpu().tv_gpu_wiener_apply(_t(rec.contiguous()), w, h, B, _t(cf), _t(out), _stream(rec)))
+    _check(_gpu().tv_gpu_wiener_apply(_t(rec.contiguous()), w, h, B, _t(cf), _t(out), stream(rec.device)))
     return out
 
 
@@ -225,7 +170,7 @@ def wiener_stats(src, rec, direction: int, other):
         h, w = rec.shape
         st = np.zeros((n_units(w, h), 9), np.int64)
         _core().tv_av1_wiener_stats(_p(np.ascontiguousarray(src)), _p(np.ascontiguousarray(rec)), w, h, direction,
-                                    _p(np.ascontiguousarray(other, np.int32), C.c_int32), _p(st, C.c_int64))
+                                    _p(np.ascontiguousarray(other, np.int32)), _p(st))
         return st
     import torch
 
@@ -233,7 +178,7 @@ def wiener_stats(src, rec, direction: int, other):
     st = torch.empty((B, n_units(w, h), 9), dtype=torch.int64, device=rec.device)
     oth = torch.as_tensor(np.asarray(other, np.int32)).to(rec.device).reshape(B, -1, 3).contiguous()
     _check(_gpu().tv_gpu_wiener_stats(_t(src.contiguous()), _t(rec.contiguous()), w, h, B, direction, _t(oth),
-                                      _t(st), _stream(rec)))
+                                      _t(st), stream(rec.device)))
     return st
 
 
@@ -251,15 +196,14 @@ def sgr_stats(src, rec, sgr_set: int):
     if _is_np(rec):
         h, w = rec.shape
         st = np.zeros((n_units(w, h), 5), np.int64)
-        _core().tv_av1_sgr_stats(_p(np.ascontiguousarray(src)), _p(np.ascontiguousarray(rec)), w, h, sgr_set,
-                                 _p(st, C.c_int64))
+        _core().tv_av1_sgr_stats(_p(np.ascontiguousarray(src)), _p(np.ascontiguousarray(rec)), w, h, sgr_set, _p(st))
         return st
     import torch
 
     B, h, w = rec.shape
     st = torch.empty((B, n_units(w, h), 5), dtype=torch.int64, device=rec.device)
     _check(_gpu().tv_gpu_sgr_stats(_t(src.contiguous()), _t(rec.contiguous()), w, h, B, sgr_set, _t(st),
-                                   _stream(rec)))
+                                   stream(rec.device)))
     return st
 
 
@@ -268,8 +212,7 @@ def sgr_apply(rec, params):
     if _is_np(rec):
         h, w = rec.shape
         out = np.empty_like(rec)
-        _core().tv_av1_sgr_apply(_p(np.ascontiguousarray(rec)), w, h,
-                                 _p(np.ascontiguousarray(params, np.int32), C.c_int32), _p(out))
+        _core().tv_av1_sgr_apply(_p(np.ascontiguousarray(rec)), w, h, _p(np.ascontiguousarray(params, np.int32)), _p(out))
         return out
     import torch
 
@@ -279,7 +222,7 @@ def sgr_apply(rec, params):
         pr = params.to(device=rec.device, dtype=torch.int32).reshape(B, -1, 3).contiguous()
     else:
         pr = torch.as_tensor(np.asarray(params, np.int32)).to(rec.device).reshape(B, -1, 3).contiguous()
-    _check(_gpu().tv_gpu_sgr_apply(_t(rec.contiguous()), w, h, B, _t(pr), _t(out), _stream(rec)))
+    _check(_gpu().tv_gpu_sgr_apply(_t(rec.contiguous()), w, h, B, _t(pr), _t(out), stream(rec.device)))
     return out
 
 
@@ -444,10 +387,9 @@ def deblock(rec, info, chroma: bool = False, sharpness: int = 0, estep: int = 4)
     if _is_np(rec):
         h, w = rec.shape
         out = np.empty_like(rec)
-        rc = _core().tv_av1_deblock(_p(np.ascontiguousarray(rec)), w, h, int(chroma),
-                                    _p(np.ascontiguousarray(info, np.uint32), C.c_uint32), sharpness, _p(out))
-        if rc != 0:
-            raise RuntimeError(_core().tv_av1_last_error().decode())
+        ok(_core().tv_av1_deblock(_p(np.ascontiguousarray(rec)), w, h, int(chroma),
+                                  _p(np.ascontiguousarray(info, np.uint32)), sharpness, _p(out)),
+           _core(), "tv_av1_last_error")
         return out
     import torch
 
@@ -457,7 +399,7 @@ def deblock(rec, info, chroma: bool = False, sharpness: int = 0, estep: int = 4)
     inf = info.to(device=rec.device, dtype=torch.int32).reshape(B, h // 4, w // 4).contiguous()
     out = torch.empty_like(rec)
     _check(_gpu().tv_gpu_av1_deblock_step(_t(rec.contiguous()), _t(out), w, h, B, int(chroma), _t(inf), sharpness,
-                                          estep, _stream(rec)))
+                                          estep, stream(rec.device)))
     return out
 
 
@@ -531,10 +473,9 @@ def range_coder_roundtrip(symbols, alphabet, contexts, adapt: bool = True):
     dec = np.zeros_like(sym)
     buf = Bytes()
     lib = _core()
-    rc = lib.tv_av1_rc_roundtrip(sym.ctypes.data_as(_vp), alp.ctypes.data_as(_vp), ctx.ctypes.data_as(_vp), len(sym),
-                                 int(ctx.max()) + 1 if len(ctx) else 1, int(adapt), _vp(buf.h), dec.ctypes.data_as(_vp))
-    if rc != 0:
-        raise RuntimeError(lib.tv_av1_last_error().decode())
+    ok(lib.tv_av1_rc_roundtrip(_p(sym), _p(alp), _p(ctx), len(sym),
+                               int(ctx.max()) + 1 if len(ctx) else 1, int(adapt), buf.h, _p(dec)),
+       lib, "tv_av1_last_error")
     return buf.tobytes(), dec
 
 
@@ -547,9 +488,7 @@ def txfm_basis(kind: str | int, n: int) -> np.ndarray:
     """(n, n) int32 basis of a 1-D AV1 transform (row k = basis function k)."""
     t = TX_TYPES.get(kind, kind)
     out = np.zeros((n, n), np.int32)
-    lib = _core()
-    lib.tv_av1_txfm_basis.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32)]
-    if lib.tv_av1_txfm_basis(int(t), n, _p(out, C.c_int32)) != 0:
+    if _core().tv_av1_txfm_basis(int(t), n, _p(out)) != 0:
         raise ValueError(f"unsupported transform {kind} x {n}")
     return out
 
@@ -566,10 +505,8 @@ def txfm2d(blocks, col: str = "dct", row: str = "dct", inverse: bool = False):
         x = np.ascontiguousarray(blocks, np.int16)
         out = np.empty_like(x)
         lib = _core()
-        lib.tv_av1_txfm_ref.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_int16)] + [C.c_int] * 5
-        lib.tv_av1_txfm_ref.restype = C.c_int
-        if lib.tv_av1_txfm_ref(_p(x, C.c_int16), _p(out, C.c_int16), nblk, log2n, tc, tr, int(inverse)) != 0:
-            raise ValueError(lib.tv_av1_last_error().decode())
+        ok(lib.tv_av1_txfm_ref(_p(x), _p(out), nblk, log2n, tc, tr, int(inverse)),
+           lib, "tv_av1_last_error", ValueError)
         return out
     import torch
 
@@ -581,9 +518,6 @@ def txfm2d(blocks, col: str = "dct", row: str = "dct", inverse: bool = False):
     x = blocks.to(torch.int16).contiguous()
     out = torch.empty_like(x)
     lib = _gpu()
-    lib.tv_gpu_av1_txfm.restype = C.c_int
-    lib.tv_av1_txfm_last_error.restype = C.c_char_p
-    rc = lib.tv_gpu_av1_txfm(_t(x), _t(out), nblk, log2n, int(inverse), _t(bc), _t(br), _stream(x))
-    if rc != 0:
-        raise RuntimeError(lib.tv_av1_txfm_last_error().decode())
+    ok(lib.tv_gpu_av1_txfm(_t(x), _t(out), nblk, log2n, int(inverse), _t(bc), _t(br), stream(x.device)),
+       lib, "tv_av1_txfm_last_error")
     return out

@@ -5,9 +5,9 @@ never as a silent substitute for a GPU tensor).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
+
+from .._native import dptr as _p, gpu_lib, ok, stream
 
 _MAT = {
     True: (0.2126, 0.7152, 0.0722, -0.1146, -0.3854, 0.5, 0.5, -0.4542, -0.0458),
@@ -88,25 +88,8 @@ def tonemap_pq_ref(y16: np.ndarray, uv16: np.ndarray, src_peak: float = 1000.0, 
 
 # ------------------------------------------------------------------ GPU wrappers
 def _call(name, *args):
-    import torch  # noqa: F401
-
-    from .._native import gpu_lib
-
     lib = gpu_lib()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        lib.tv_ops_last_error.restype = C.c_char_p
-        raise RuntimeError(lib.tv_ops_last_error().decode())
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    import torch
-
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    ok(getattr(lib, name)(*args), lib, "tv_ops_last_error")
 
 
 def _planes(h, w, dev):
@@ -123,7 +106,7 @@ def rgb_to_i420(rgb, bt709: bool = True):
     rgb = rgb.contiguous()
     h, w, _ = rgb.shape
     y, u, v = _planes(h, w, rgb.device)
-    _call("tv_rgb_to_i420", _p(rgb), w, h, w * 3, _p(y), _p(u), _p(v), int(bt709), _stream(rgb))
+    _call("tv_rgb_to_i420", _p(rgb), w, h, w * 3, _p(y), _p(u), _p(v), int(bt709), stream(rgb.device))
     return y, u, v
 
 
@@ -133,7 +116,8 @@ def p010_to_i420(y16, uv16):
         return p010_to_i420_ref(y16, uv16)
     h, w = y16.shape
     y, u, v = _planes(h, w, y16.device)
-    _call("tv_p010_to_i420", _p(y16.contiguous()), _p(uv16.contiguous()), w, h, _p(y), _p(u), _p(v), _stream(y16))
+    _call("tv_p010_to_i420", _p(y16.contiguous()), _p(uv16.contiguous()), w, h, _p(y), _p(u), _p(v),
+          stream(y16.device))
     return y, u, v
 
 
@@ -143,5 +127,5 @@ def tonemap_pq(y16, uv16, src_peak: float = 1000.0, dst_peak: float = 100.0):
     h, w = y16.shape
     y, u, v = _planes(h, w, y16.device)
     _call("tv_tonemap_pq", _p(y16.contiguous()), _p(uv16.contiguous()), w, h, _p(y), _p(u), _p(v),
-          C.c_float(src_peak), C.c_float(dst_peak), _stream(y16))
+          src_peak, dst_peak, stream(y16.device))
     return y, u, v

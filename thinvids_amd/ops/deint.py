@@ -62,17 +62,14 @@ def bwdif_plane(prev, cur, nxt, tff: bool = True):
         return bwdif_plane_ref(prev, cur, nxt, tff)
     import torch
 
-    from .._native import gpu_lib
+    from .._native import gpu_lib, ok, stream
 
     h, w = cur.shape
     out = torch.empty_like(cur)
     lib = gpu_lib()
-    p = lambda t: C.c_void_p(t.contiguous().data_ptr())
-    rc = lib.tv_bwdif_plane(p(prev), p(cur), p(nxt), C.c_void_p(out.data_ptr()), w, h, int(tff),
-                            C.c_void_p(torch.cuda.current_stream(cur.device).cuda_stream))
-    if rc != 0:
-        lib.tv_ops_last_error.restype = C.c_char_p
-        raise RuntimeError(lib.tv_ops_last_error().decode())
+    p = lambda t: t.contiguous().data_ptr()
+    ok(lib.tv_bwdif_plane(p(prev), p(cur), p(nxt), out.data_ptr(), w, h, int(tff), stream(cur.device)),
+       lib, "tv_ops_last_error")
     return out
 
 
@@ -83,14 +80,13 @@ def deinterlace_device(df, tff: bool = True):
     same layout."""
     import torch
 
-    from .._native import gpu_lib
+    from .._native import gpu_lib, ok, stream
     from .stage import DevFrames
 
     if df.bits != 8:
         raise ValueError("bwdif: 8-bit frames only")
     out = torch.empty_like(df.buf)
     lib = gpu_lib()
-    stream = C.c_void_p(torch.cuda.current_stream(df.buf.device).cuda_stream)
     esz = df.buf.element_size()
     if any(st != pw for _, pw, _, st, _ in df.planes):
         raise ValueError("bwdif: planes must be packed")
@@ -100,15 +96,10 @@ def deinterlace_device(df, tff: bool = True):
     if any(p[4] != fs for p in df.planes) or any(r + pw * ph > fs for r, (_, pw, ph, _, _) in zip(rel, df.planes)):
         raise ValueError("bwdif: planes of one frame must share the frame stride")
     npl = len(df.planes)
-    f = lib.tv_bwdif_segment
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_int),
-                  C.POINTER(C.c_int), C.c_int, C.c_void_p]
-    rc = f(C.c_void_p(df.buf.data_ptr() + base * esz), C.c_void_p(out.data_ptr() + base * esz), fs * esz, df.n, npl,
-           (C.c_long * npl)(*[r * esz for r in rel]), (C.c_int * npl)(*[p[1] for p in df.planes]),
-           (C.c_int * npl)(*[p[2] for p in df.planes]), int(tff), stream)
-    if rc != 0:
-        lib.tv_ops_last_error.restype = C.c_char_p
-        raise RuntimeError(lib.tv_ops_last_error().decode())
+    ok(lib.tv_bwdif_segment(df.buf.data_ptr() + base * esz, out.data_ptr() + base * esz, fs * esz, df.n, npl,
+                            (C.c_long * npl)(*[r * esz for r in rel]), (C.c_int * npl)(*[p[1] for p in df.planes]),
+                            (C.c_int * npl)(*[p[2] for p in df.planes]), int(tff), stream(df.buf.device)),
+       lib, "tv_ops_last_error")
     return DevFrames(out, df.n, df.w, df.h, df.planes, df.bits, [df.buf, *df.keep])
 
 

@@ -7,8 +7,6 @@ batch of frames in one launch.  numpy frames take the reference path.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 _FONT = {
@@ -79,7 +77,7 @@ def stamp_frames_gpu(frames_dev, w: int, h: int, numbers, size: int = 72, border
     [n, Y|U|V] (I420, w x h), in place, with one kernel launch."""
     import torch
 
-    from .._native import gpu_lib
+    from .. import _native
 
     texts = [str(int(n)) for n in numbers]
     masks = [label_mask(t, size, border) for t in texts]
@@ -91,11 +89,7 @@ def stamp_frames_gpu(frames_dev, w: int, h: int, numbers, size: int = 72, border
         stack[i, oy:oy + m.shape[0], ox:ox + m.shape[1]] = m
     x0, y0 = placement(w, h, mw, mh)
     dm = torch.from_numpy(stack).to(frames_dev.device)
-    lib = gpu_lib()
-    stream = torch.cuda.current_stream(frames_dev.device).cuda_stream
-    rc = lib.tv_overlay_mask(C.c_void_p(frames_dev.data_ptr()), len(texts), w, h, C.c_void_p(dm.data_ptr()), mw, mh,
-                             x0, y0, C.c_void_p(stream))
-    if rc != 0:
-        lib.tv_ops_last_error.restype = C.c_char_p
-        raise RuntimeError(lib.tv_ops_last_error().decode())
+    lib = _native.gpu_lib()
+    _native.ok(lib.tv_overlay_mask(frames_dev.data_ptr(), len(texts), w, h, dm.data_ptr(), mw, mh, x0, y0,
+                                   _native.stream(frames_dev.device)), lib, "tv_ops_last_error")
     return frames_dev

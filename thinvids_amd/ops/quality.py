@@ -3,8 +3,6 @@ on a 4-sample grid (x264/libvpx convention); HIP kernel `k_ssim` for GPU tensors
 numpy reference for numpy inputs."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 C1, C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
@@ -35,16 +33,13 @@ def ssim(a, b) -> float:
         return ssim_ref(a, b)
     import torch
 
-    from .._native import gpu_lib
+    from .._native import gpu_lib, ok, stream
 
     h, w = a.shape
     acc = torch.zeros(1, dtype=torch.float64, device=a.device)
     lib = gpu_lib()
-    rc = lib.tv_ssim_plane(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), w, h, a.stride(0), b.stride(0),
-                           C.c_void_p(acc.data_ptr()), C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    if rc != 0:
-        lib.tv_ops_last_error.restype = C.c_char_p
-        raise RuntimeError(lib.tv_ops_last_error().decode())
+    ok(lib.tv_ssim_plane(a.data_ptr(), b.data_ptr(), w, h, a.stride(0), b.stride(0), acc.data_ptr(),
+                         stream(a.device)), lib, "tv_ops_last_error")
     n = ((w - 8) // 4 + 1) * ((h - 8) // 4 + 1)
     return float(acc.item()) / n
 

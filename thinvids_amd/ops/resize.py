@@ -8,7 +8,6 @@ array / CPU tensor runs the float64 reference of the same separable filter.
 """
 from __future__ import annotations
 
-import ctypes as C
 from functools import lru_cache
 
 import numpy as np
@@ -74,7 +73,7 @@ def resize_plane(src, out_h: int, out_w: int, a: int = 3, out=None):
 
     if not src.is_cuda:
         return torch.from_numpy(resize_plane_ref(src.numpy(), out_h, out_w, a))
-    from .._native import gpu_lib
+    from .._native import gpu_lib, ok, stream
 
     lib = gpu_lib()
     h, w = src.shape
@@ -85,14 +84,9 @@ def resize_plane(src, out_h: int, out_w: int, a: int = 3, out=None):
     tmp = torch.empty((h, out_w), dtype=torch.int16, device=dev)
     if out is None:
         out = torch.empty((out_h, out_w), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    vp = C.c_void_p
-    rc = lib.tv_resize_plane(vp(src.data_ptr()), w, h, w, vp(out.data_ptr()), out_w, out_h, out.stride(0),
-                             vp(ix.data_ptr()), vp(wx.data_ptr()), tx, vp(iy.data_ptr()), vp(wy.data_ptr()), ty,
-                             vp(tmp.data_ptr()), vp(stream))
-    if rc != 0:
-        lib.tv_ops_last_error.restype = C.c_char_p
-        raise RuntimeError(lib.tv_ops_last_error().decode())
+    ok(lib.tv_resize_plane(src.data_ptr(), w, h, w, out.data_ptr(), out_w, out_h, out.stride(0), ix.data_ptr(),
+                           wx.data_ptr(), tx, iy.data_ptr(), wy.data_ptr(), ty, tmp.data_ptr(), stream(dev)),
+       lib, "tv_ops_last_error")
     return out
 
 

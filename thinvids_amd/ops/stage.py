@@ -21,32 +21,15 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .._native import gpu_lib, ok, stream
 from ..models.hevc import coded_size
 
 
-def _lib():
-    from .._native import gpu_lib
-
-    lib = gpu_lib()
-    if not getattr(lib, "_stage_sigs", False):
-        vp, ci, cl = C.c_void_p, C.c_int, C.c_long
-        lib.tv_pad_batch.argtypes = [vp, ci, ci, ci, cl, vp, ci, ci, ci, cl, ci, vp]
-        lib.tv_synth_batch.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_int), C.c_uint32, vp]
-        lib.tv_stage_last_error.restype = C.c_char_p
-        lib.tv_resize_batch.argtypes = [vp, ci, ci, ci, cl, vp, ci, ci, ci, cl, ci, ci, ci,
-                                        vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, vp]
-        lib.tv_tonemap_pq_batch.argtypes = [vp, vp, ci, ci, ci, vp, C.c_float, C.c_float, vp]
-        lib.tv_ops_last_error.restype = C.c_char_p
-        lib.tv_thumbs8_batch.argtypes = [vp, ci, ci, ci, ci, cl, ci, vp, vp]
-        lib._stage_sigs = True
-    return lib
+_lib = gpu_lib
 
 
 def _ok(rc: int, which: str = "stage") -> None:
-    if rc != 0:
-        lib = _lib()
-        msg = lib.tv_stage_last_error() if which == "stage" else lib.tv_ops_last_error()
-        raise RuntimeError(msg.decode())
+    ok(rc, gpu_lib(), f"tv_{which}_last_error")
 
 
 @dataclass
@@ -107,10 +90,7 @@ def from_flat(t, w: int, h: int, n: int | None = None, bits: int = 8) -> DevFram
 def thumbs8(ptr: int, bits: int, w: int, h: int, stride: int, fs: int, n: int, out) -> None:
     """8x8 block means of n luma planes at device address `ptr` (element strides) into the
     float32 CUDA tensor `out` [n][h // 8][w // 8], on the current stream."""
-    import torch
-
-    st = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    _ok(_lib().tv_thumbs8_batch(C.c_void_p(ptr), bits, w, h, stride, fs, n, C.c_void_p(out.data_ptr()), st))
+    _ok(_lib().tv_thumbs8_batch(ptr, bits, w, h, stride, fs, n, out.data_ptr(), stream(out.device)))
 
 
 def upload_frames(frames, device) -> DevFrames:
@@ -150,8 +130,7 @@ def synth_frames(seed: int, w: int, h: int, starts, device) -> DevFrames:
     ysz, csz = cw * ch, (cw // 2) * (ch // 2)
     buf = torch.empty(n * (ysz + 2 * csz), dtype=torch.uint8, device=device)
     ts = (C.c_int * n)(*[int(t) for t in starts])
-    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    _ok(_lib().tv_synth_batch(C.c_void_p(buf.data_ptr()), w, h, n, ts, seed & 0xFFFFFFFF, st))
+    _ok(_lib().tv_synth_batch(buf.data_ptr(), w, h, n, ts, seed & 0xFFFFFFFF, stream(device)))
     planes = [(0, w, h, cw, ysz), (n * ysz, w // 2, h // 2, cw // 2, csz),
               (n * ysz + n * csz, w // 2, h // 2, cw // 2, csz)]
     return DevFrames(buf, n, w, h, planes, 8)
@@ -179,9 +158,8 @@ def tone_map(src: DevFrames, src_peak: float = 1000.0, dst_peak: float = 100.0) 
     uv16 = torch.stack([u, v], -1).reshape(n, h // 2, w).to(torch.int16).contiguous()
     fsz = w * h * 3 // 2
     out = torch.empty((n, fsz), dtype=torch.uint8, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _ok(_lib().tv_tonemap_pq_batch(y16.data_ptr(), uv16.data_ptr(), w, h, n, out.data_ptr(), C.c_float(src_peak),
-                                   C.c_float(dst_peak), st), "ops")
+    _ok(_lib().tv_tonemap_pq_batch(y16.data_ptr(), uv16.data_ptr(), w, h, n, out.data_ptr(), src_peak, dst_peak,
+                                   stream(dev)), "ops")
     res = DevFrames(out, n, w, h, flat_layout(w, h), 8)
     res.keep = [y16, uv16]
     return res
@@ -208,7 +186,7 @@ def to_staging(src: DevFrames, out_w: int, out_h: int, dst, frame0: int = 0, cod
     src = tone_map(src)
     lib = _lib()
     dev = dst.device
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = stream(dev)
     fsz, planes = staging_planes(out_w, out_h, coded)
     base = dst.data_ptr() + frame0 * fsz
     for c, (doff, dw, dh, dstride, pw, ph) in enumerate(planes):
@@ -245,20 +223,14 @@ def read_y4m_device(src, start: int, n: int, device, threads: int | None = None,
     n = max(0, min(n, src.nframes - start))
     nbytes = n * info.frame_bytes
     lib = _lib()
-    if not getattr(lib, "_ingest_sigs", False):
-        lib.tv_ingest_h2d.argtypes = [C.c_char_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong,
-                                      C.c_int, C.c_void_p, C.POINTER(C.c_double)]
-        lib.tv_ingest_last_error.restype = C.c_char_p
-        lib._ingest_sigs = True
     if threads is None:
         threads = max(1, min(12, len(os.sched_getaffinity(0))))
     ring = _Pinned.get(2 * threads * INGEST_CHUNK)
     esz = 2 if info.bits > 8 else 1
     buf = torch.empty(nbytes // esz, dtype=torch.int16 if esz == 2 else torch.uint8, device=device)
     tm = (C.c_double * 2)()
-    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    if lib.tv_ingest_h2d(src.path.encode(), info.header_len + start * info.frame_bytes, nbytes,
-                         C.c_void_p(buf.data_ptr()), C.c_void_p(ring.data_ptr()), ring.numel(), threads, st, tm) != 0:
+    if lib.tv_ingest_h2d(src.path.encode(), info.header_len + start * info.frame_bytes, nbytes, buf.data_ptr(),
+                         ring.data_ptr(), ring.numel(), threads, stream(device), tm) != 0:
         raise RuntimeError(f"{src.path}: ingest of frames {start}..{start + n} failed: "
                            f"{lib.tv_ingest_last_error().decode()}")
     w, h = info.width, info.height

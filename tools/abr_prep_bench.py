@@ -45,8 +45,8 @@ def main():
                 out["synth_ms_per_frame"] = round(timed(lambda: lad.synth_p010(0, n)), 4)
                 lad.synth_p010(0, n)
                 out["tonemap_ms_per_frame"] = round(timed(lambda: lad.lib.tv_tonemap_pq_batch(
-                    lad.y16.data_ptr(), lad.uv16.data_ptr(), sw, sh, n, lad.sdr.data_ptr(),
-                    __import__("ctypes").c_float(1000.0), __import__("ctypes").c_float(100.0), lad._stream())), 4)
+                    lad.y16.data_ptr(), lad.uv16.data_ptr(), sw, sh, n, lad.sdr.data_ptr(), 1000.0, 100.0,
+                    lad._stream())), 4)
             lad.synth_p010(0, n)
             out[f"ladder_chunk_ms_per_frame_{key}"] = round(timed(lambda: lad.ladder_chunk(0, n)), 4)
             lad.close()
