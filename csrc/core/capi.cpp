@@ -10,6 +10,7 @@
 #include "tv/cpu_encoder.h"
 #include "tv/hevc_codec.h"
 #include "tv/me_model.h"
+#include "tv/sdh.h"
 #include "tv/synth.h"
 #include "tv/tb_frag.h"
 
@@ -64,7 +65,7 @@ void* tv_cpu_encoder_new(int width, int height, int qp, int deblock, int range, 
   cfg.width = width;
   cfg.height = height;
   cfg.qp = qp;
-  cfg.set_flags(deblock);  // 1 deblocking, 2 SAO, 4 WPP, 8 no RQT, 16 no intra-in-P
+  cfg.set_flags(deblock);  // 1 deblocking, 2 SAO, 4 WPP, 8 no RQT, 16 no intra-in-P, ... (SeqConfig::set_flags)
   cfg.max_merge_cand = max_merge;
   cfg.finalize();
   CpuEncoder* e = nullptr;  // a bad config becomes tv_last_error, not an abort across the FFI
@@ -155,10 +156,18 @@ void tv_cpu_encoder_decisions(void* e, uint8_t* cu_log2, uint8_t* intra, uint8_t
   std::memcpy(mv, d.mv.data(), d.mv.size() * 2);
   std::memcpy(cbf, d.cbf.data(), d.cbf.size());
 }
+// the level planes (coded size, int16) of the last encoded frame
+void tv_cpu_encoder_levels(void* e, int16_t* cy, int16_t* cu, int16_t* cv) {
+  const FrameDecisions& d = static_cast<CpuEncoder*>(e)->dec;
+  std::memcpy(cy, d.coef_y.data(), d.coef_y.size() * 2);
+  std::memcpy(cu, d.coef_u.data(), d.coef_u.size() * 2);
+  std::memcpy(cv, d.coef_v.data(), d.coef_v.size() * 2);
+}
 
 // ---------------------------- decisions -> reconstruction / bitstream ---------------------
 // Reconstruct a frame from externally supplied decisions (golden model for the GPU).
 // src/ref/rec planes are coded size. coef planes are outputs.  ref may be null for intra.
+// `deblock`: non-zero = deblocking; bit 512 (SeqConfig::set_flags) sign data hiding.
 int tv_reconstruct_frame(int width, int height, int qp, int deblock, const uint8_t* src_y,
                          const uint8_t* src_u, const uint8_t* src_v, const uint8_t* ref_y,
                          const uint8_t* ref_u, const uint8_t* ref_v, const uint8_t* cu_log2,
@@ -170,7 +179,8 @@ int tv_reconstruct_frame(int width, int height, int qp, int deblock, const uint8
     cfg.width = width;
     cfg.height = height;
     cfg.qp = qp;
-    cfg.deblock = deblock != 0;
+    cfg.deblock = (deblock & ~512) != 0;
+    cfg.sign_hiding = (deblock & 512) != 0;
     cfg.rqt = false;  // no transform splits (tv_write_frame codes every split flag as 0)
     cfg.finalize();
     const int W = cfg.coded_w, H = cfg.coded_h;
@@ -203,7 +213,8 @@ int tv_reconstruct_frame(int width, int height, int qp, int deblock, const uint8
   });
 }
 
-// Write parameter sets (if idr) + a slice NAL from decision arrays.
+// Write parameter sets (if idr) + a slice NAL from decision arrays (`deblock` as above: with
+// bit 512 the level planes must satisfy the hidden signs' parity, else this fails).
 int tv_write_frame(int width, int height, int qp, int deblock, int max_merge, int idr, int poc,
                    const uint8_t* cu_log2, const uint8_t* intra, const uint8_t* ipm,
                    const int16_t* mv, const uint8_t* cbf, const int16_t* cy, const int16_t* cu,
@@ -213,7 +224,8 @@ int tv_write_frame(int width, int height, int qp, int deblock, int max_merge, in
     cfg.width = width;
     cfg.height = height;
     cfg.qp = qp;
-    cfg.deblock = deblock != 0;
+    cfg.deblock = (deblock & ~512) != 0;
+    cfg.sign_hiding = (deblock & 512) != 0;
     cfg.max_merge_cand = max_merge;
     cfg.finalize();  // no tu plane: inter CUs code split_transform_flag 0
     FrameData f;
@@ -337,6 +349,16 @@ void tv_quant_levels(const int* coef, int n, int qp, int log2N, int* ref, int* f
   for (int i = 0; i < n; ++i) {
     ref[i] = quant_level(coef[i], qp, log2N, false);
     fast[i] = quant_fast(coef[i], q);
+  }
+}
+// sign data hiding: ref[i] = sdh_delta of coef[i] and its quant_level (tv/sdh.h), fast[i] = the
+// 32-bit sdh_delta_fast of the GPU paths
+void tv_sdh_deltas(const int* coef, int n, int qp, int log2N, int intra, int* ref, int* fast) {
+  const QuantParams q = quant_params(qp, log2N);
+  for (int i = 0; i < n; ++i) {
+    const int l = quant_level(coef[i], qp, log2N, intra != 0);
+    ref[i] = sdh_delta(coef[i], l, qp, log2N);
+    fast[i] = sdh_delta_fast(coef[i], l, q);
   }
 }
 int tv_demux_mp4(const uint8_t* mp4, size_t n, int* w, int* h, int* nframes, int* timescale,

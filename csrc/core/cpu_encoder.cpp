@@ -20,6 +20,7 @@
 #include "tv/cpu_encoder.h"
 #include "tv/me_model.h"
 #include "tv/rc_model.h"
+#include "tv/sdh.h"
 
 namespace tv {
 
@@ -452,7 +453,8 @@ void analyze_inter_b(const SeqConfig& cfg, const Picture& src, const Picture& re
 
 // -------------------------------- reconstruction ----------------------------------------
 // Transform + quantise one TB of residual; writes levels into the plane; returns cbf.
-static int code_tb(const int* resid, int log2N, int qp, bool intra, int16_t* lev, int ls, int rdoq) {
+// sdh_scan >= 0: sign data hiding (tv/sdh.h) with that scan index for the TB's 4x4 groups.
+static int code_tb(const int* resid, int log2N, int qp, bool intra, int16_t* lev, int ls, int rdoq, int sdh_scan) {
   const int N = 1 << log2N;
   int coef[32 * 32];
   forward_transform(resid, log2N, coef);
@@ -497,6 +499,26 @@ static int code_tb(const int* resid, int log2N, int qp, bool intra, int16_t* lev
       for (int i = 0; i < N; ++i) lev[j * ls + i] = 0;
     nz = 0;
   }
+  // sign data hiding on the final levels; coef still holds what quant_level received
+  if (sdh_scan >= 0 && nz) {
+    for (int gy = 0; gy < N; gy += 4)
+      for (int gx = 0; gx < N; gx += 4) {
+        auto at = [&](int n) {
+          int x, y;
+          coef_pos_in_sb(sdh_scan, n, x, y);
+          return (gy + y) * N + gx + x;
+        };
+        auto lv = [&](int n) -> int16_t& {
+          const int p = at(n);
+          return lev[(p >> log2N) * ls + (p & (N - 1))];
+        };
+        int pos, value;
+        if (sdh_adjust([&](int n) { return (int)lv(n); },
+                       [&](int n) { return sdh_delta(coef[at(n)], lv(n), qp, log2N); },
+                       [&](int n) { return coef[at(n)] < 0; }, pos, value))
+          lv(pos) = (int16_t)value;
+      }
+  }
   return nz ? 1 : 0;
 }
 
@@ -526,7 +548,8 @@ void reconstruct_frame(const SeqConfig& cfg, const Picture& src, const Picture* 
         for (int i = 0; i < n; ++i) resid[j * n + i] = S[j * stride + i] - pred[j * n + i];
       int16_t* L = (c == 0 ? fd.coef_y : (c == 1 ? fd.coef_u : fd.coef_v)).data() + (size_t)y * stride + x;
       const int qq = c ? qpc : qp;
-      const int cb = code_tb(resid, l2, qq, intra, L, stride, cfg.rdoq ? kRdoqMode : 0);
+      const int cb = code_tb(resid, l2, qq, intra, L, stride, cfg.rdoq ? kRdoqMode : 0,
+                             cfg.sign_hiding ? scan_idx_for(intra, l2, c, fd.ipm[u]) : -1);
       cbf |= cb << c;
       recon_tb(L, stride, cb, l2, qq, pred, rec.plane(c) + (size_t)y * stride + x, stride);
     }

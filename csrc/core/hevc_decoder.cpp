@@ -105,7 +105,6 @@ Pps parse_pps(BitReader& br) {
   if (br.u(1)) fail("output_flag_present unsupported");
   if (br.u(3)) fail("extra slice header bits unsupported");
   p.sign_hiding = br.u(1) != 0;
-  if (p.sign_hiding) fail("sign data hiding unsupported");
   if (br.u(1)) fail("cabac_init_present unsupported");
   br.ue();
   br.ue();
@@ -137,9 +136,8 @@ class SliceDecoder {
   SliceDecoder(const Sps& sps, const Pps& pps, int stype, int qp, int max_merge, BitReader* br,
                Picture* cur, const Picture* const* ref, const int* ref_poc, int poc, FrameDecisions* fd, bool sao,
                std::vector<size_t> row_start = {})
-      : sps_(sps), islice_(stype == 2), bslice_(stype == 0), qp_(qp), max_merge_(max_merge), dec_(br), br_(br),
+      : sps_(sps), sign_hiding_(pps.sign_hiding), islice_(stype == 2), bslice_(stype == 0), qp_(qp), max_merge_(max_merge), dec_(br), br_(br),
         cur_(cur), ref_(ref[0]), ref1_(ref[1]), poc_(poc), fd_(fd), sao_(sao), row_start_(std::move(row_start)) {
-    (void)pps;
     ref_poc_[0] = ref_poc[0];
     ref_poc_[1] = ref_poc[1];
     ctx_.init(islice_ ? 0 : (bslice_ ? 2 : 1), qp);
@@ -640,8 +638,11 @@ class SliceDecoder {
         }
       }
       if (firstG2 >= 0 && bin(CTX_G2 + ctxSet + (cIdx ? 4 : 0))) absv[firstG2] = 3;
+      // 7.3.8.11: signHidden = lastSigScanPos - firstSigScanPos > 3 (pos[] is in reverse scan
+      // order); the hidden coeff_sign_flag is not in the stream
+      const bool signHidden = sign_hiding_ && pos[0] - pos[cnt - 1] > 3;
       int signs[16];
-      for (int k = 0; k < cnt; ++k) signs[k] = dec_.decode_bypass();
+      for (int k = 0; k < cnt; ++k) signs[k] = (signHidden && k == cnt - 1) ? 0 : dec_.decode_bypass();
       int rice = 0;
       bool firstC2 = true;
       for (int k = 0; k < cnt; ++k) {
@@ -651,6 +652,11 @@ class SliceDecoder {
           if (absv[k] > 3 * (1 << rice)) rice = tv_min(rice + 1, 4);
         }
         if (absv[k] >= 2) firstC2 = false;
+      }
+      if (signHidden) {  // 7.4.9.11: sumAbsLevel odd at firstSigScanPos -> the level is negated
+        int sumAbs = 0;
+        for (int k = 0; k < cnt; ++k) sumAbs += absv[k];
+        signs[cnt - 1] = sumAbs & 1;
       }
       for (int k = 0; k < cnt; ++k) {
         int xc, yc;
@@ -709,6 +715,7 @@ class SliceDecoder {
   }
 
   const Sps& sps_;
+  const bool sign_hiding_;  // pps sign_data_hiding_enabled_flag
   bool islice_, bslice_;
   int qp_, max_merge_;
   CabacDecoder dec_;

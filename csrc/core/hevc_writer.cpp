@@ -14,6 +14,7 @@
 #include "tv/bitstream.h"
 #include "tv/cabac.h"
 #include "tv/hevc_codec.h"
+#include "tv/sdh.h"
 
 namespace tv {
 
@@ -140,7 +141,7 @@ void write_parameter_sets(const SeqConfig& cfg, std::vector<uint8_t>& out) {
     bw.put(0, 1);  // dependent_slice_segments_enabled_flag
     bw.put(0, 1);  // output_flag_present_flag
     bw.put(0, 3);  // num_extra_slice_header_bits
-    bw.put(0, 1);  // sign_data_hiding_enabled_flag
+    bw.put(cfg.sign_hiding ? 1 : 0, 1);  // sign_data_hiding_enabled_flag
     bw.put(0, 1);  // cabac_init_present_flag
     bw.ue(0);      // num_ref_idx_l0_default_active_minus1
     bw.ue(0);      // num_ref_idx_l1_default_active_minus1
@@ -859,9 +860,19 @@ class SliceWriter {
         }
       });
       if (firstG2 >= 0) bin(absv[firstG2] > 2, CTX_G2 + ctxSet + (cIdx ? 4 : 0));
+      // sign data hiding: the sign of the group's first level in scan order (the last one
+      // here) is not coded; the levels must already carry it in their parity (tv/sdh.h)
+      int nsign = cnt;
+      if (cfg_.sign_hiding && sdh_hidden(m)) {
+        int sum = 0;
+        for (int k = 0; k < cnt; ++k) sum += absv[k];
+        if ((sum & 1) != signs[cnt - 1])
+          throw std::runtime_error("sign data hiding: a coefficient group's parity does not match its hidden sign");
+        --nsign;
+      }
       uint32_t sbits = 0;
-      for (int k = 0; k < cnt; ++k) sbits = (sbits << 1) | (uint32_t)signs[k];
-      enc_.encode_bypass_bins(sbits, cnt);
+      for (int k = 0; k < nsign; ++k) sbits = (sbits << 1) | (uint32_t)signs[k];
+      enc_.encode_bypass_bins(sbits, nsign);
       int rice = 0;
       bool firstC2 = true;
       for (int k = 0; k < cnt; ++k) {

@@ -341,6 +341,8 @@ class Core {
     g_.rdoq = seq_.rdoq ? kRdoqMode : 0;
     seq_.subpel_satd = (c.deblock & 256) != 0;
     g_.subpel_satd = seq_.subpel_satd ? 1 : 0;
+    seq_.sign_hiding = (c.deblock & 512) != 0;
+    g_.sign_hiding = seq_.sign_hiding ? 1 : 0;
     seq_.mgop = c.mgop;
     if (c.mgop > 1) {
       const GopPlan gp = plan_gop(2 * c.mgop + 1, c.mgop);
@@ -739,6 +741,7 @@ class Core {
     a.pic.ref_poc[1] = pic.ref[1];
     a.pic.sao = seq_.sao;
     a.pic.rqt = seq_.rqt;
+    a.pic.sign_hiding = seq_.sign_hiding;
     a.pic.max_merge = seq_.max_merge_cand;
     a.dec = dec;
     a.cs = slot_compact(s);

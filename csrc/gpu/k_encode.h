@@ -117,6 +117,7 @@ struct EntropyPic {
   int poc;         // B slices: POCs for the AMVP scaling
   int ref_poc[2];
   int sao, rqt, max_merge;
+  int sign_hiding;  // pps sign_data_hiding_enabled_flag (tv/sdh.h)
 };
 // context init states [initType][SliceQpY][ctx] (state | valMps << 6) and the coder tables
 struct EntropyTables {

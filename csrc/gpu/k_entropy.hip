@@ -22,6 +22,7 @@
 #include "k_encode.h"
 #include "tv/cabac.h"
 #include "tv/hevc_mvpred.h"
+#include "tv/sdh.h"
 
 namespace tv {
 namespace gpu {
@@ -516,7 +517,9 @@ struct CtbBinariser {
         }
       }
       if (g2 >= 0) bin(g2, CTX_G2 + ctxSet + (cIdx ? 4 : 0));
-      if (cnt) s.bypass(sbits, cnt);
+      // sign data hiding: the group's first level in scan order came last and keeps no sign bin
+      const int hid = (p.sign_hiding && sdh_hidden(m)) ? 1 : 0;
+      if (cnt - hid) s.bypass(sbits >> hid, cnt - hid);
       int rice = 0, k = 0;
       bool firstC2 = true;
       for (unsigned sm = m; sm; ++k) {

@@ -24,6 +24,7 @@
 #include "wave_tb.h"
 #include "tv/me_model.h"
 #include "tv/rc_model.h"
+#include "tv/sdh.h"
 
 namespace tv {
 namespace gpu {
@@ -1042,8 +1043,20 @@ struct PReconLds {
   int mv[16][2];              // per 8x8 unit (raster within the CTB)
   int mv1[16][2];             // B pictures: list-1 vectors and directions
   int dir[16];
-  uint8_t bwin[4][15 * 16];   // per wave: 15x15 luma reference window of a bi unit
-  int16_t bh[4][15 * 8];      // per wave: horizontal filter pass (15 rows x 8)
+  union {
+    struct {
+      uint8_t bwin[4][15 * 16];   // per wave: 15x15 luma reference window of a bi unit
+      int16_t bh[4][15 * 8];      // per wave: horizontal filter pass (15 rows x 8)
+    };
+    // k_inter_recon<true> (sign data hiding), written by stage 2 when the prediction buffers
+    // above are dead: per coefficient sdh_delta + 64 as a byte (inter rounding: -64 <= d < 192;
+    // luma 32x32, Cb 16x16, Cr 16x16), and per lane's four coefficients of a row the bits
+    // "coefficient r < 0" (a zero level takes its sign from there)
+    struct {
+      alignas(4) uint8_t sdh_d[32 * 32 + 2 * 16 * 16];
+      uint8_t sdh_neg[(32 * 32 + 2 * 16 * 16) / 4];
+    };
+  };
   int nz[48], sa[48], dc[48];  // per-TB statistics: luma 0..15, Cb 16..31, Cr 32..47
   int qtype[4];               // luma quadrant: 0 part of a 32x32 CU, 1 16x16 CU, 2 four 8x8 CUs
   int tzero[8];               // stage-3/4 tile t has no surviving level: reconstruction = prediction
@@ -1069,6 +1082,7 @@ __device__ __forceinline__ int pr_tb_chroma(const PReconLds& L, int p, int x, in
   const int base = 16 + 16 * p;
   return t == 0 ? base : (t == 1 ? base + 4 * q : base + 4 * q + ((y >> 2) & 1) * 2 + ((x >> 2) & 1));
 }
+static_assert(sizeof(PReconLds) == 22096, "k_inter_recon: 7 workgroups of PReconLds per CU");
 // a TB whose only non-zero level is a lone +-1 outside DC is dropped (tv code_tb, inter)
 __device__ __forceinline__ bool pr_zeroed(const PReconLds& L, int id) {
   return L.nz[id] == 0 || (L.nz[id] == 1 && L.sa[id] == 1 && L.dc[id] == 0);
@@ -1076,6 +1090,10 @@ __device__ __forceinline__ bool pr_zeroed(const PReconLds& L, int id) {
 
 // 7 waves per SIMD: 72 VGPRs and no scratch (8 would need 64 and spills), and 7 workgroups
 // of PReconLds (22096 B) are what fits the CU's 160 KiB of LDS.
+// kSdh (SeqConfig::sign_hiding, tv/sdh.h): stage 2 also keeps every coefficient's distance
+// from its level, and a pass after RDOQ-lite adjusts one level of each coefficient group whose
+// parity does not carry its hidden sign.  <false> compiles none of it.
+template <bool kSdh>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) k_inter_recon(FrameSet src, FrameSet ref, const uint8_t* phase,
                                                      FrameSet rec, DecisionSet dec, Geo g,
                                                      FrameSet ref1, const uint8_t* phase1) {
@@ -1364,13 +1382,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
   // TBs are 4-aligned, so the levels are one 8-byte store, the TB statistics one pair of LDS
   // atomics per lane, and only the first column can be the TB's origin.  multi: some TB has
   // >= 2 levels -- this lane adds two, or finds the count already non-zero.
-  auto emit_levels = [&](int16_t* dst, int id, int sh2, const QuantParams& q, const int* v, bool origin) {
+  // kSdh: di = the lane's first coefficient in sdh_d (luma y * 32 + x, chroma 1024 + 256 pl + y * 16 + x)
+  auto emit_levels = [&](int16_t* dst, int id, int sh2, const QuantParams& q, const int* v, bool origin, int di) {
     int cnt = 0, sum = 0, lev[4];
+    uint32_t dd = 0, neg = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      lev[r] = quant_fast((v[r] + (1 << (sh2 - 1))) >> sh2, q);
+      const int cf = (v[r] + (1 << (sh2 - 1))) >> sh2;
+      lev[r] = quant_fast(cf, q);
       cnt += lev[r] != 0;
       sum += tv_abs(lev[r]);
+      if constexpr (kSdh) {
+        dd |= (uint32_t)(sdh_delta_fast(cf, lev[r], q) + 64) << (8 * r);
+        neg |= (cf < 0 ? 1u : 0u) << r;
+      }
+    }
+    if constexpr (kSdh) {
+      *reinterpret_cast<uint32_t*>(&L.sdh_d[di]) = dd;
+      L.sdh_neg[di >> 2] = (uint8_t)neg;
     }
     *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)(lev[0] & 0xffff) | (uint32_t)lev[1] << 16,
                                                 (uint32_t)(lev[2] & 0xffff) | (uint32_t)lev[3] << 16);
@@ -1397,12 +1426,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
       const QuantParams qy = quant_params(qp, l2);
       const int m = (1 << l2) - 1, y = (t >> 1) * 16 + fi, x = (t & 1) * 16 + kq * 4;
       const int id = whole ? 0 : 4 * t + (l2 == 3 ? (fi >> 3) * 2 + (kq >> 1) : 0);
-      emit_levels(&L.resY[y * 32 + x], id, l2 + 6, qy, o, (x & m) == 0 && (y & m) == 0);
+      emit_levels(&L.resY[y * 32 + x], id, l2 + 6, qy, o, (x & m) == 0 && (y & m) == 0, kSdh ? y * 32 + x : 0);
     } else if (whole) {
       const int pl = t - 4;
       const int ia = fi * kTmpCP + 4 * kq;
       frag_tile_split_a(frag4(&L.tmpCh[pl][ia]), frag4(&L.tmpCl[pl][ia]), C16(4, 0), o);
-      emit_levels(&L.resC[pl][fi * 16 + kq * 4], 16 + 16 * pl, 10, quant_params(qpc, 4), o, lane == 0);
+      emit_levels(&L.resC[pl][fi * 16 + kq * 4], 16 + 16 * pl, 10, quant_params(qpc, 4), o, lane == 0,
+                  kSdh ? 1024 + 256 * pl + fi * 16 + kq * 4 : 0);
     } else {
       const int q = t - 4, ox = (q & 1) * 8, oy = (q >> 1) * 8, l2 = L.qtype[q] == 1 ? 3 : 2;
       // A(r = fi, k = 4 kq ..): inside plane fi >> 3's block iff pin; the read is in bounds either way
@@ -1413,7 +1443,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
       if (pin) {
         const int m = (1 << l2) - 1, pl = fi >> 3, y = oy + (fi & 7), x = ox + 4 * (kq & 1);
         const int id = 16 + 16 * pl + 4 * q + (l2 == 2 ? ((fi >> 2) & 1) * 2 + (kq & 1) : 0);
-        emit_levels(&L.resC[pl][y * 16 + x], id, l2 + 6, qc, o, (x & m) == 0 && (y & m) == 0);
+        emit_levels(&L.resC[pl][y * 16 + x], id, l2 + 6, qc, o, (x & m) == 0 && (y & m) == 0,
+                    kSdh ? 1024 + 256 * pl + y * 16 + x : 0);
       }
     }
   }
@@ -1470,6 +1501,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
       for (int j = 0; j < 4; ++j) *reinterpret_cast<uint2*>(p + j * st) = make_uint2(0u, 0u);
       atomicSub(&L.nz[id], 1);
       atomicSub(&L.sa[id], 1);
+    }
+    __syncthreads();
+  }
+  // ---- sign data hiding (tv/sdh.h) on the final levels: after RDOQ-lite, only in TBs the
+  // lone-level rule keeps, and without touching nz / sa / dc -- a TB that now looks like a lone
+  // +-1 stays.  One thread per 4x4 group as above; inter TBs scan diagonally.  (A quadrant that
+  // is an intra CU is coded again, whole, by k_pintra_recon.)
+  if constexpr (kSdh) {
+    if (tid < 96) {
+      int16_t* p;
+      int st, di, id;
+      if (tid < 64) {
+        const int x = (tid & 7) * 4, y = (tid >> 3) * 4;
+        id = pr_tb_luma(L, x, y);
+        p = &L.resY[y * 32 + x], st = 32, di = y * 32 + x;
+      } else {
+        const int c = tid - 64, pl = c >> 4, x = (c & 3) * 4, y = ((c & 15) >> 2) * 4;
+        id = pr_tb_chroma(L, pl, x, y);
+        p = &L.resC[pl][y * 16 + x], st = 16, di = 1024 + 256 * pl + y * 16 + x;
+      }
+      if (!pr_zeroed(L, id)) {
+        auto at = [&](int n) {
+          const int s = sdh_scan_pos(0, n);
+          return (s >> 2) * st + (s & 3);
+        };
+        int pos, value;
+        if (sdh_adjust([&](int n) { return (int)p[at(n)]; }, [&](int n) { return (int)L.sdh_d[di + at(n)] - 64; },
+                       [&](int n) { const int a = di + at(n); return ((L.sdh_neg[a >> 2] >> (a & 3)) & 1) != 0; }, pos, value))
+          p[at(pos)] = (int16_t)value;
+      }
     }
     __syncthreads();
   }
@@ -1668,7 +1729,7 @@ void launch_inter_frame(FrameSet src, FrameSet ref, const uint8_t* phase, FrameS
   const dim3 grid(g.wc * g.hc, B);
   (g.subpel_satd ? k_inter_me<true> : k_inter_me<false>)<<<grid, kMeThreads, 0, s>>>(src, ref, phase, dec, me.prev_mv, me.cmv, g, rc, range, nullptr, pi ? *pi : none);
   if (pi) launch_pintra_decide(src, dec, g, rc, *pi, B, s);
-  k_inter_recon<<<grid, 256, 0, s>>>(src, ref, phase, rec, dec, g, FrameSet{}, nullptr);
+  (g.sign_hiding ? k_inter_recon<true> : k_inter_recon<false>)<<<grid, 256, 0, s>>>(src, ref, phase, rec, dec, g, FrameSet{}, nullptr);
   if (pi) launch_pintra_recon(src, rec, dec, g, *pi, B, s);
 }
 
@@ -1682,7 +1743,7 @@ void launch_inter_frame_b(FrameSet src, FrameSet ref0, const uint8_t* phase0, Fr
   k_me<<<grid, kMeThreads, 0, s>>>(src, ref0, phase0, dec, me0.prev_mv, me0.cmv, g, rc, range[0], meout, none);
   k_me<<<grid, kMeThreads, 0, s>>>(src, ref1, phase1, dec, me1.prev_mv, me1.cmv, g, rc, range[1], o1, none);
   k_bi_decide<<<grid, 256, 0, s>>>(src, phase0, phase1, meout, o1, dec, g, rc);
-  k_inter_recon<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, ref1, phase1);
+  (g.sign_hiding ? k_inter_recon<true> : k_inter_recon<false>)<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, ref1, phase1);
 }
 
 }  // namespace gpu

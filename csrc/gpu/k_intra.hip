@@ -199,6 +199,8 @@ struct CompLdsT {
 };
 using CompLds = CompLdsT<32>;
 
+// kSdh (SeqConfig::sign_hiding): wave_code_tb<true> adjusts the levels for sign data hiding.
+template <bool kSdh>
 __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec, DecisionSet dec, Geo g, int diag,
                                                      int cy0) {
   const int b = blockIdx.y, c = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -342,8 +344,8 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
       L.resid[i] = (int16_t)((int)L.src[(y - by + py) * S + (x - bx + px)] - p);
     }
     wave_sync();
-    const int cb = wave_code_tb(L.resid, L.pred, l2, qpx, true, coefp + (long)y * pw + x, pw,
-                                &L.rec[(y - by) * S + (x - bx)], S, Tm, L.tb);
+    const int cb = wave_code_tb<kSdh>(L.resid, L.pred, l2, qpx, true, coefp + (long)y * pw + x, pw,
+                                      &L.rec[(y - by) * S + (x - bx)], S, Tm, L.tb, scan_idx_for(true, l2, c, mode));
     if (lane == 0 && cb) atomicOr(&cbfs[k], 1u << c);
   }
   __syncthreads();
@@ -368,7 +370,7 @@ void launch_intra_frame(FrameSet src, FrameSet rec, DecisionSet dec, const Geo& 
     const int cy0 = tv_max(0, (d - (g.wc - 1) + 1) / 2);
     const int cy1 = tv_min(g.hc - 1, d / 2);
     if (cy1 < cy0) continue;
-    k_intra_recon<<<dim3(cy1 - cy0 + 1, B), 192, 0, s>>>(src, rec, dec, g, d, cy0);
+    (g.sign_hiding ? k_intra_recon<true> : k_intra_recon<false>)<<<dim3(cy1 - cy0 + 1, B), 192, 0, s>>>(src, rec, dec, g, d, cy0);
   }
 }
 
@@ -504,6 +506,7 @@ struct PIntraLds {
   WaveTbScratch tb;
 };
 
+template <bool kSdh>
 __global__ void __launch_bounds__(192) k_pintra_recon(FrameSet src, FrameSet rec, DecisionSet dec, Geo g,
                                                       PIntraBuffers pi, int q, int B) {
   const int c = threadIdx.x >> 6, lane = threadIdx.x & 63, nctu = g.wc * g.hc;
@@ -584,8 +587,8 @@ __global__ void __launch_bounds__(192) k_pintra_recon(FrameSet src, FrameSet rec
     }
     wave_sync();
     int16_t* coefp = (c == 0 ? dec.coef_y + b * g.ysz : (c == 1 ? dec.coef_u : dec.coef_v) + b * g.csz);
-    const int cbit = wave_code_tb(L.resid, L.pred, l2, c ? chroma_qp(qp, 0) : qp, true, coefp + (long)y * pw + x, pw,
-                                  Rp + (long)y * pw + x, pw, Tm, L.tb);
+    const int cbit = wave_code_tb<kSdh>(L.resid, L.pred, l2, c ? chroma_qp(qp, 0) : qp, true, coefp + (long)y * pw + x, pw,
+                                        Rp + (long)y * pw + x, pw, Tm, L.tb, scan_idx_for(true, l2, c, mode));
     if (lane == 0 && cbit) atomicOr(&cbfs, 1u << c);
     __syncthreads();
     if (threadIdx.x < 4)
@@ -603,7 +606,8 @@ void launch_pintra_decide(FrameSet src, DecisionSet dec, const Geo& g, const RcT
 
 void launch_pintra_recon(FrameSet src, FrameSet rec, DecisionSet dec, const Geo& g, const PIntraBuffers& pi, int B,
                          hipStream_t s) {
-  for (int q = 0; q < 4; ++q) k_pintra_recon<<<128, 192, 0, s>>>(src, rec, dec, g, pi, q, B);
+  const auto k = g.sign_hiding ? k_pintra_recon<true> : k_pintra_recon<false>;
+  for (int q = 0; q < 4; ++q) k<<<128, 192, 0, s>>>(src, rec, dec, g, pi, q, B);
 }
 
 }  // namespace gpu

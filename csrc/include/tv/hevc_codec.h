@@ -53,13 +53,17 @@ struct SeqConfig {
   // half- / quarter-pel motion vectors chosen by Hadamard SATD + MV rate instead of SAD + MV
   // rate (tv/me_model.h, "SATD sub-pel decision"); off by default
   bool subpel_satd = false;
+  // sign data hiding (sign_data_hiding_enabled_flag; tv/sdh.h): the sign of the first level of a
+  // coefficient group is carried by the parity of its magnitudes; off by default
+  bool sign_hiding = false;
   // All of these change the bitstream: they are explicit configuration (the C API's flag bits 3 / 4,
   // EncodeSpec.rqt / .pintra, part of the engine key and the checkpoint fingerprint), never
   // read from the environment here.
   // Flag bits of the C API's `deblock` argument: 1 deblocking, 2 SAO, 4 WPP, 8 no RQT,
   // 16 no intra-in-P (32: GPU engine only, CABAC on the host), 64 I P P P QP cascade,
-  // 128 no RDOQ-lite, 256 SATD sub-pel decision
+  // 128 no RDOQ-lite, 256 SATD sub-pel decision, 512 sign data hiding
   void set_flags(int f) {
+    sign_hiding = (f & 512) != 0;
     subpel_satd = (f & 256) != 0;
     deblock = (f & 1) != 0;
     sao = (f & 2) != 0;

@@ -47,12 +47,14 @@ CORE = {
     "tv_cpu_encoder_encode_qp": (i, [vp, u8p, u8p, u8p, i, i, i, i, i, vp]),
     "tv_cpu_encoder_recon": (None, [vp, u8p, u8p, u8p]),
     "tv_cpu_encoder_decisions": (None, [vp, u8p, u8p, u8p, i16p, u8p]),
+    "tv_cpu_encoder_levels": (None, [vp, i16p, i16p, i16p]),
     "tv_reconstruct_frame": (i, [i] * 4 + [u8p] * 9 + [i16p, u8p, i16p, i16p, i16p, u8p, u8p, u8p]),
     "tv_write_frame": (i, [i] * 7 + [u8p, u8p, u8p, i16p, u8p, i16p, i16p, i16p, vp]),
     "tv_mv_rate": (None, [i32p, i32p, i, i32p, i32p]),
     "tv_av1_mv_comp_bits": (None, [i32p, i, i32p]),
     "tv_tb_frag_expand": (i, [i, i32p]),
     "tv_quant_levels": (None, [i32p, i, i, i, i32p, i32p]),
+    "tv_sdh_deltas": (None, [i32p, i, i, i, i, i32p, i32p]),
     "tv_hevc_spec_table": (i, [cstr, i32p, i]),
     # HEVC decoder
     "tv_decoder_new": (vp, []),

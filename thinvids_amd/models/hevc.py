@@ -40,14 +40,14 @@ def psnr_yuv(ref: Frame, dec: Frame) -> dict:
 
 
 def codec_flags(deblock: bool = True, sao: bool = False, wpp: bool = True, rqt: bool = True, pintra: bool = True,
-                cascade: bool = False, rdoq: bool = True, subpel_satd: bool = False) -> int:
+                cascade: bool = False, rdoq: bool = True, subpel_satd: bool = False, sign_hiding: bool = False) -> int:
     """The native APIs' configuration bits (tv::SeqConfig::set_flags): 1 deblocking, 2 SAO,
     4 WPP substreams, 8 no residual quadtree, 16 no intra CUs in P pictures, 64 the constant-QP
     I P P P QP cascade (tv/gop.h ippp_qp_offset), 128 no RDOQ-lite coefficient-group trimming
     (tv/hevc_defs.h kRdoqMode), 256 half- / quarter-pel vectors chosen by SATD + MV rate
-    (tv/me_model.h; off by default)."""
+    (tv/me_model.h; off by default), 512 sign data hiding (tv/sdh.h; off by default)."""
     return (int(bool(deblock)) | (2 if sao else 0) | (4 if wpp else 0) | (0 if rqt else 8) | (0 if pintra else 16)
-            | (64 if cascade else 0) | (0 if rdoq else 128) | (256 if subpel_satd else 0))
+            | (64 if cascade else 0) | (0 if rdoq else 128) | (256 if subpel_satd else 0) | (512 if sign_hiding else 0))
 
 
 IPPP_CASCADE_IDR = -5
@@ -66,19 +66,20 @@ class CpuEncoder:
     def __init__(self, width: int, height: int, qp: int = 27, deblock: bool = True,
                  search_range: int = 64, max_merge: int = 5, sao: bool = False, crf: int = 0, wpp: bool = True,
                  bframes: int = 1, rqt: bool = True, pintra: bool = True, cascade: bool = True, rdoq: bool = True,
-                 subpel_satd: bool = False):
+                 subpel_satd: bool = False, sign_hiding: bool = False):
         """`wpp`: one CABAC substream per CTB row (entropy_coding_sync; the GPU engine's
         default, it codes them on the device); `rqt` / `pintra` / `rdoq`: residual quadtree for
         inter CUs, intra 16x16 CUs in P pictures, trailing lone-level coefficient groups of inter
         TBs dropped; `subpel_satd`: sub-pel motion vectors chosen by Hadamard SATD instead of SAD,
-        off by default (coding tools; part of the bitstream identity)."""
+        off by default; `sign_hiding`: sign data hiding (tv/sdh.h), off by default (coding tools;
+        part of the bitstream identity)."""
         if width % 2 or height % 2:
             raise ValueError("width/height must be even")
         self.lib = core_lib()
         self.width, self.height, self.qp = width, height, qp
         self.cw, self.ch = coded_size(width, height)
         self.bframes = int(bframes)
-        flags = codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd)
+        flags = codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding)
         if self.bframes > 1:
             if crf:
                 raise ValueError("CRF with B frames is not supported by the golden encoder")
@@ -130,6 +131,14 @@ class CpuEncoder:
                                           ptr(d["cbf"]))
         d["mv"] = mv
         return d
+
+    def levels(self) -> tuple:
+        """The level planes (Y, U, V; coded size, int16) of the last encoded frame."""
+        cy = np.empty((self.ch, self.cw), np.int16)
+        cu = np.empty((self.ch // 2, self.cw // 2), np.int16)
+        cv = np.empty_like(cu)
+        self.lib.tv_cpu_encoder_levels(self.h, ptr(cy), ptr(cu), ptr(cv))
+        return cy, cu, cv
 
 
 def gop_plan(nframes: int, bframes: int) -> dict:
@@ -233,12 +242,13 @@ def decode(annexb: bytes, coded: bool = True, first: int = 0, count: int = -1) -
 
 
 def write_frame(width: int, height: int, qp: int, idr: bool, poc: int, dec: dict,
-                coef: tuple, deblock: bool = True, max_merge: int = 5) -> bytes:
-    """Entropy-code one frame from decision arrays (cu_log2/intra/ipm/mv/cbf + coef planes)."""
+                coef: tuple, deblock: bool = True, max_merge: int = 5, sign_hiding: bool = False) -> bytes:
+    """Entropy-code one frame from decision arrays (cu_log2/intra/ipm/mv/cbf + coef planes).
+    `sign_hiding`: the stream hides signs (tv/sdh.h); levels that break the parity raise."""
     lib = core_lib()
     out = Bytes()
     cy, cu, cv = (np.ascontiguousarray(c, dtype=np.int16) for c in coef)
-    check(lib.tv_write_frame(width, height, qp, int(deblock), max_merge, int(idr), poc,
+    check(lib.tv_write_frame(width, height, qp, int(bool(deblock)) | (512 if sign_hiding else 0), max_merge, int(idr), poc,
                              ptr(np.ascontiguousarray(dec["cu_log2"])), ptr(np.ascontiguousarray(dec["intra"])),
                              ptr(np.ascontiguousarray(dec["ipm"])),
                              ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16)),
@@ -248,7 +258,7 @@ def write_frame(width: int, height: int, qp: int, idr: bool, poc: int, dec: dict
 
 
 def reconstruct_reference(width: int, height: int, qp: int, src: Frame, ref: Frame | None,
-                          dec: dict, deblock: bool = True):
+                          dec: dict, deblock: bool = True, sign_hiding: bool = False):
     """Golden-model pass B: decisions -> (cbf, coef planes, recon) on the CPU."""
     lib = core_lib()
     cw, ch = coded_size(width, height)
@@ -263,7 +273,7 @@ def reconstruct_reference(width: int, height: int, qp: int, src: Frame, ref: Fra
     r = [np.ascontiguousarray(p) for p in ref] if ref is not None else None
     null = C.cast(None, C.POINTER(C.c_uint8))
     check(lib.tv_reconstruct_frame(
-        width, height, qp, int(deblock), ptr(s[0]), ptr(s[1]), ptr(s[2]),
+        width, height, qp, int(bool(deblock)) | (512 if sign_hiding else 0), ptr(s[0]), ptr(s[1]), ptr(s[2]),
         ptr(r[0]) if r else null, ptr(r[1]) if r else null, ptr(r[2]) if r else null,
         ptr(np.ascontiguousarray(dec["cu_log2"])), ptr(np.ascontiguousarray(dec["intra"])),
         ptr(np.ascontiguousarray(dec["ipm"])), ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16)),

@@ -1077,6 +1077,8 @@ def main(argv=None) -> int:
     ap.add_argument("--no-rdoq", dest="rdoq", action="store_false", help="HEVC: no RDOQ-lite coefficient-group trimming")
     ap.add_argument("--subpel-satd", dest="subpel_satd", action="store_true",
                     help="HEVC: sub-pel motion vectors chosen by SATD + MV rate (off by default)")
+    ap.add_argument("--sign-hiding", dest="sign_hiding", action="store_true",
+                    help="HEVC: sign data hiding (off by default)")
     ap.add_argument("--deinterlace", action="store_true", help="bwdif every segment (DVD-native interlaced sources)")
     a = ap.parse_args(argv)
     import torch
@@ -1096,7 +1098,8 @@ def main(argv=None) -> int:
     res = run_job(a.input, a.output, a.height, a.qp, a.gop, a.segment_frames, a.mode, a.bitrate_kbps, ladder,
                   software=a.software, resume_dir=a.resume_dir, max_retries=a.max_retries, bframes=a.bframes,
                   tools={"wpp": a.wpp, "rqt": a.rqt, "pintra": a.pintra, "cascade": a.cascade, "rdoq": a.rdoq,
-                         **({"subpel_satd": True} if a.subpel_satd else {})},
+                         **({"subpel_satd": True} if a.subpel_satd else {}),
+                         **({"sign_hiding": True} if a.sign_hiding else {})},
                   deinterlace=a.deinterlace)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res), flush=True)

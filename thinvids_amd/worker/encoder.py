@@ -55,6 +55,7 @@ class EncodeSpec:
     cascade: bool = True  # constant-QP I P P P: the low-delay QP cascade (tv/gop.h)
     rdoq: bool = True  # inter TBs drop trailing lone-+-1 coefficient groups (tv/hevc_defs.h)
     subpel_satd: bool = False  # sub-pel motion vectors chosen by SATD + MV rate (tv/me_model.h)
+    sign_hiding: bool = False  # sign data hiding: one sign per coefficient group in the parity (tv/sdh.h)
     # where the WPP substreams are CABAC-coded ("auto" / "gpu" / "host"): the same bytes, so
     # not a coding tool (not in tools() / the checkpoint fingerprint), but its own engine
     entropy: str = "auto"
@@ -63,13 +64,16 @@ class EncodeSpec:
         if self.codec == "av1":
             return ("av1", self.width, self.height, self.av1_qindex(), self.cascade)
         return (self.width, self.height, self.qp, self.gop, self.search_range, self.deblock, self.sao, self.seed,
-                self.crf, self.hevc_bframes(), self.wpp, self.rqt, self.pintra, self.cascade, self.rdoq, self.entropy, self.subpel_satd)
+                self.crf, self.hevc_bframes(), self.wpp, self.rqt, self.pintra, self.cascade, self.rdoq, self.entropy, self.subpel_satd,
+                self.sign_hiding)
 
     def tools(self) -> dict:
         """The coding-tool switches as GpuEngine / CpuEncoder keyword arguments."""
         t = {"wpp": self.wpp, "rqt": self.rqt, "pintra": self.pintra, "cascade": self.cascade, "rdoq": self.rdoq}
         if self.subpel_satd:  # only when on: the fingerprints of existing jobs do not change
             t["subpel_satd"] = True
+        if self.sign_hiding:
+            t["sign_hiding"] = True
         return t
 
     def hevc_bframes(self) -> int:

@@ -35,7 +35,7 @@ def run_point(args):
     import numpy as np
 
     kw = dict(sao=a["sao"], rqt=a["rqt"], pintra=a["pintra"], wpp=a["wpp"], cascade=a["ippp_cascade"], rdoq=a["rdoq"],
-              subpel_satd=a["subpel_satd"])
+              subpel_satd=a["subpel_satd"], sign_hiding=a.get("sign_hiding", False))
     if a.get("engine") == "gpu":
         return run_point_gpu(qp, a, w, h, seed, fq, kw)
     if a.get("codec") == "av1":
@@ -108,6 +108,7 @@ def main():
     ap.add_argument("--wpp", type=int, default=int(env_on("TV_WPP")))
     ap.add_argument("--rdoq", type=int, default=1, help="RDOQ-lite coefficient-group trimming")
     ap.add_argument("--subpel-satd", type=int, default=0, help="sub-pel vectors chosen by SATD + MV rate (tv/me_model.h)")
+    ap.add_argument("--sign-hiding", type=int, default=0, help="sign data hiding (tv/sdh.h)")
     ap.add_argument("--engine", choices=("cpu", "gpu"), default="cpu", help="gpu: run the points on the GPU engine, one after another")
     ap.add_argument("--anchor", default="")
     ap.add_argument("--out", default="")
@@ -116,6 +117,7 @@ def main():
                cascade=[int(x) for x in a.cascade.split(",")] if a.cascade else [], iqp=a.iqp,
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
                ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
+               sign_hiding=bool(a.sign_hiding),
                engine=a.engine)
     qps = [int(q) for q in a.qps.split(",")]
     if a.engine == "gpu":

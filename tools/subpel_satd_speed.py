@@ -7,6 +7,9 @@ through GpuEngine.encode_synthetic, off and on alternately, every measurement in
 process (one process owns the GPU at a time).  Prints one JSON line per child and a summary
 (median frames/s of both, bytes and PSNR-Y of the last step).  With --once the process runs a
 single untimed step of --tool and exits: the command to put under a kernel profiler.
+
+main(tool, script) measures any opt-in GpuEngine / EncodeSpec switch the same way
+(tools/sign_hiding_speed.py).
 """
 from __future__ import annotations
 
@@ -22,17 +25,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def child(a) -> None:
+def child(a, tool: str) -> None:
     from thinvids_amd.models.gpu_engine import GpuEngine
     from thinvids_amd.worker.encoder import EncodeSpec, auto_batch, device_budget
 
     w, h = map(int, a.res.split("x"))
     on = a.tool == "on"
-    spec = EncodeSpec(w, h, qp=a.qp, gop=a.gop, sao=True, subpel_satd=on)
+    spec = EncodeSpec(w, h, qp=a.qp, gop=a.gop, sao=True, **{tool: on})
     batch = a.batch or auto_batch(spec, device_budget(0))
     seed = 1 | ((1 << 31) if a.textured else 0)
     eng = GpuEngine(width=w, height=h, qp=a.qp, batch=batch, gop=a.gop, search_range=64, sao=True, seed=seed,
-                    subpel_satd=on)
+                    **{tool: on})
     starts = lambda i: [(i * batch + b) * a.gop for b in range(batch)]  # noqa: E731
     if a.once:
         eng.encode_synthetic(starts(0))
@@ -51,7 +54,8 @@ def child(a) -> None:
     print(json.dumps(out), flush=True)
 
 
-def main() -> None:
+def main(tool: str = "subpel_satd", script: str = os.path.abspath(__file__)) -> None:
+    """`tool`: the switch to alternate; `script`: the file the children run (it calls this)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", default="1920x1080")
     ap.add_argument("--qp", type=int, default=27)
@@ -66,21 +70,21 @@ def main() -> None:
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.tool:
-        child(a)
+        child(a, tool)
         return
-    common = [sys.executable, os.path.abspath(__file__), "--res", a.res, "--qp", str(a.qp), "--gop", str(a.gop),
+    common = [sys.executable, script, "--res", a.res, "--qp", str(a.qp), "--gop", str(a.gop),
               "--batch", str(a.batch), "--steps", str(a.steps), "--warmup", str(a.warmup)] + (["--textured"] if a.textured else [])
     runs = []
     for _ in range(a.rounds):
-        for tool in ("off", "on"):
-            p = subprocess.run(common + ["--tool", tool], capture_output=True, text=True, timeout=600)
+        for state in ("off", "on"):
+            p = subprocess.run(common + ["--tool", state], capture_output=True, text=True, timeout=600)
             if p.returncode != 0:  # a failed child ends the measurement: nothing more is started
                 sys.stderr.write(p.stdout + p.stderr)
-                raise SystemExit(f"child ({tool}) exited with {p.returncode}")
+                raise SystemExit(f"child ({state}) exited with {p.returncode}")
             runs.append(json.loads(p.stdout.strip().splitlines()[-1]))
             print(json.dumps(runs[-1]), flush=True)
     med = {t: statistics.median(r["frames_per_s"] for r in runs if r["tool"] == t) for t in ("off", "on")}
-    res = {"config": {"res": a.res, "qp": a.qp, "gop": a.gop, "textured": a.textured, "steps": a.steps, "warmup": a.warmup},
+    res = {"config": {"tool": tool, "res": a.res, "qp": a.qp, "gop": a.gop, "textured": a.textured, "steps": a.steps, "warmup": a.warmup},
            "runs": runs, "median_frames_per_s": med, "on_over_off": round(med["on"] / med["off"], 4)}
     print(json.dumps(res["median_frames_per_s"] | {"on_over_off": res["on_over_off"]}), flush=True)
     if a.out:
