@@ -1829,7 +1829,7 @@ int satd_block(const int* a, const int* b, int N) {
 }
 }  // namespace
 
-GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qidx0, const int* qmap) {
+GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qidx0, const int* qmap, int tools) {
   GoldenOut out;
   const int nb = g.nblk();
   // TV_AV1_DBG (conformance bring-up): 1 no deblocking, 2 no CDEF, 4 no loop restoration,
@@ -1865,10 +1865,11 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
       for (int y = 0; y < g.H + 2 * kPad; ++y)
         for (int x = 0; x < pw; ++x) padY[(size_t)y * pw + x] = (uint8_t)ry(x - kPad, y - kPad);
     }
-    // intra blocks, inter blocks at a given MV (force_mv), or the motion search alone
+    // intra blocks (every block of a key frame; as_intra: an accepted intra block of an inter
+    // frame, tv/av1_enc.h), inter blocks at a given MV (force_mv), or the motion search alone
     // (search_out: the block's MV, nothing coded)
     int frame_rnd = kRndInter;
-    auto code_block = [&](int by, int bx, const uint32_t* force_mv, uint32_t* search_out) {
+    auto code_block = [&](int by, int bx, const uint32_t* force_mv, uint32_t* search_out, bool as_intra = false) {
         const int b = by * g.bw + bx;
         int s[3][256], pred[3][256], rc[256];
         for (int p = 0; p < 3; ++p) {
@@ -1879,7 +1880,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
         }
         int ym = 0, uvm = 0, inter = 0;
         uint32_t mvw = 0;
-        if (fd.fp.key) {
+        if (fd.fp.key || as_intra) {
           int best = 1 << 30;
           // TV_AV1_DBG bit 32: the search also tries D113 / D135 / D157 (conformance tests of
           // the directional predictor; the shipped search leaves them out, av1_enc.h)
@@ -1970,7 +1971,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
             for (int j = 0; j < N; ++j) P[(size_t)(by * N + i) * w + bx * N + j] = (uint8_t)rc[i * N + j];
         }
         fd.mode[b] = pack_mode(inter, ym, uvm, nz == 0, nz);
-        fd.mv[b] = mvw;
+        fd.mv[b] = inter ? mvw : 0;
     };
     if (fd.fp.key) {  // intra: left / above dependencies (raster order)
       for (int by = 0; by < g.bh; ++by)
@@ -2052,6 +2053,39 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
       parallel_rows(g.bh, [&](int by) {
         for (int bx = 0; bx < g.bw; ++bx) code_block(by, bx, &mvs[by * g.bw + bx], nullptr);
       });
+      fd.ib.assign(nb, 0);
+      if (tools & kToolIntraInInter) {
+        // intra blocks in inter frames (tv/av1_enc.h): candidates from source neighbours in
+        // parallel, acceptance from the candidate map, accepted blocks re-coded in raster order
+        parallel_rows(g.bh, [&](int by) {
+          for (int bx = 0; bx < g.bw; ++bx) {
+            const int ic = blk_satd(bx, by, mvs[by * g.bw + bx]);
+            if (!ib_gated(ic)) continue;
+            int s0[256];
+            for (int i = 0; i < 16; ++i)
+              for (int j = 0; j < 16; ++j) s0[i * 16 + j] = S.y[(size_t)(by * 16 + i) * g.W + bx * 16 + j];
+            IntraEdge e;
+            intra_edges([&](int x, int y) { return (int)S.y[(size_t)y * g.W + x]; }, bx * 16, by * 16, 16, e);
+            const int dc = intra_dc(e, 16);
+            const int best = ib_best_cost(
+                [&](int m) {
+                  int pr[256];
+                  for (int i = 0; i < 16; ++i)
+                    for (int j = 0; j < 16; ++j) pr[i * 16 + j] = intra_pred_px(m, e, 16, i, j, dc);
+                  return satd_block(s0, pr, 16);
+                },
+                lam);
+            if (ib_candidate(ic, best, lam)) fd.ib[by * g.bw + bx] = 1;
+          }
+        });
+        std::vector<uint8_t> cm(fd.ib);
+        for (int by = 0; by < g.bh; ++by)
+          for (int bx = 0; bx < g.bw; ++bx)
+            if (ib_accepted(cm.data(), g.bw, bx, by)) {
+              fd.ib[by * g.bw + bx] |= 2;
+              code_block(by, bx, nullptr, nullptr, true);
+            }
+      }
       for (int sy = 0; sy < g.sbh; ++sy)
         for (int sx = 0; sx < g.sbw; ++sx) merge_sb(fd.mode.data(), fd.mv.data(), g.bw, g.bh, sx, sy);
     }
@@ -2202,6 +2236,11 @@ const char* tv_av1c_last_error() { return g_codec_err.c_str(); }
 // Dc_Qlookup / Ac_Qlookup (8-bit) of q-index q (dc != 0: the DC table)
 int tv_av1c_qlookup(int q, int dc) { return dc ? dc_q(q) : ac_q(q); }
 
+int tv_av1c_golden_encode_tools(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, int tools,
+                                void* out, int64_t* tu_sizes, uint8_t* recon, uint32_t* mode, uint32_t* mv,
+                                int16_t* ly, int16_t* lu, int16_t* lv, int32_t* fparams, int8_t* cdef, int32_t* lr,
+                                uint8_t* ib);
+
 // Golden encode of n coded-size I420 frames (concatenated Y U V per frame) at `qidx`:
 // the temporal units go to `out` (one Bytes object) and their byte sizes to tu_sizes[n];
 // the post-filter reconstructions to recon (same layout); per-frame decisions to mode /
@@ -2210,12 +2249,22 @@ int tv_av1c_golden_encode(int dw, int dh, int n, const uint8_t* yuv, int qidx, c
                           int64_t* tu_sizes,
                           uint8_t* recon, uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv,
                           int32_t* fparams, int8_t* cdef, int32_t* lr) {
+  return tv_av1c_golden_encode_tools(dw, dh, n, yuv, qidx, qmap, 0, out, tu_sizes, recon, mode, mv, ly, lu, lv, fparams,
+                                     cdef, lr, nullptr);
+}
+
+// The same with a coding-tools word (av1_enc.h: bit 0 kToolIntraInInter); ib [n][nblk]
+// (may be null): per frame and block, bit 0 = intra candidate, bit 1 = accepted.
+int tv_av1c_golden_encode_tools(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, int tools,
+                                void* out, int64_t* tu_sizes, uint8_t* recon, uint32_t* mode, uint32_t* mv,
+                                int16_t* ly, int16_t* lu, int16_t* lv, int32_t* fparams, int8_t* cdef, int32_t* lr,
+                                uint8_t* ib) {
   return codec_guard([&] {
     const SeqGeo g = make_seq_geo(dw, dh);
     const size_t fsz = (size_t)g.W * g.H * 3 / 2;
     std::vector<Planes> src(n);
     for (int i = 0; i < n; ++i) split_planes(yuv + i * fsz, g, src[i]);
-    GoldenOut go = golden_encode(g, src, qidx, qmap);
+    GoldenOut go = golden_encode(g, src, qidx, qmap, tools);
     auto* bytes = static_cast<std::vector<uint8_t>*>(out);
     bytes->clear();
     const int nb = g.nblk();
@@ -2234,7 +2283,21 @@ int tv_av1c_golden_encode(int dw, int dh, int n, const uint8_t* yuv, int qidx, c
       if (fparams) pack_fparams(fd.fp, fparams + (size_t)i * 25);
       if (cdef) std::memcpy(cdef + (size_t)i * g.nsb(), fd.cdef_idx.data(), g.nsb());
       if (lr) std::memcpy(lr + (size_t)i * fd.lr.size(), fd.lr.data(), sizeof(int32_t) * fd.lr.size());
+      if (ib) {
+        if (fd.ib.empty()) std::memset(ib + (size_t)i * nb, 0, nb);
+        else std::memcpy(ib + (size_t)i * nb, fd.ib.data(), nb);
+      }
     }
+  });
+}
+
+// Acceptance of intra candidates (av1_enc.h ib_accepted): cand [bh][bw] bytes (bit 0 =
+// candidate) -> acc [bh][bw] (1 = accepted).
+int tv_av1c_ib_accept(const uint8_t* cand, int bw, int bh, uint8_t* acc) {
+  return codec_guard([&] {
+    if (bw < 1 || bh < 1) throw std::runtime_error("av1: bad block grid");
+    for (int by = 0; by < bh; ++by)
+      for (int bx = 0; bx < bw; ++bx) acc[by * bw + bx] = ib_accepted(cand, bw, bx, by) ? 1 : 0;
   });
 }
 

@@ -13,6 +13,9 @@
 //                  candidate modes read no above-right samples, so the frame is a plain
 //                  (rows + cols - 1)-step wavefront; 4 luma modes x 16 lanes per pass, all
 //                  7 chroma modes x 8 lanes (U + V 4x4 SATDs) in one pass.
+//   k_av1e_ib_*    opt-in intra blocks of inter frames (tv/av1_enc.h): per-block candidate
+//                  analysis on source neighbours, acceptance + per-pass lists, seven
+//                  list-driven launches of the key-frame block coder.
 //   k_av1e_lfinfo  deblocking info words (tx / block sizes, levels, skip && inter).
 //   k_av1e_cdef_choose  one workgroup per segment: greedy 8-preset CDEF table from the
 //                  k_cdef_search SSEs of the active 64x64 blocks (identical to cdef_choose).
@@ -183,12 +186,15 @@ struct Planes3W {
 // (the refined field) + residual coding + reconstruction (mvout = mvin).
 // Minimum waves per SIMD for the register allocation: stage 0 asks for 6 (<= 80 VGPRs, no
 // scratch, against the compiler's 84 / 5 waves); stage 1 is LDS-limited, left alone.
-template <int STAGE>
+// IC (stage 1 only): also write the block's inter cost (luma SATD of the source against the
+// prediction, tv/av1_enc.h "intra blocks in inter frames") to icost [B][nb].
+template <int STAGE, bool IC = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STAGE == 0 ? 6 : 1))) k_av1e_inter(Planes3 src, Planes3 ref, Planes3W rec, uint32_t* __restrict__ mode,
                                                    const uint32_t* __restrict__ mvin, uint32_t* __restrict__ mvout,
                                                    int16_t* __restrict__ ly, int16_t* __restrict__ lu,
                                                    int16_t* __restrict__ lv, int W, int H, const int* __restrict__ qarr,
-                                                   const unsigned long long* __restrict__ satd_acc) {
+                                                   const unsigned long long* __restrict__ satd_acc,
+                                                   int* __restrict__ icost) {
   __shared__ __attribute__((aligned(16))) uint8_t win[kWinN * kWinP + 8];
   __shared__ __attribute__((aligned(16))) uint8_t sblk[256];
   __shared__ __attribute__((aligned(16))) uint8_t cwin[2][kCWin * kCWin];
@@ -407,6 +413,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STAGE =
     }
   }
   __syncthreads();
+  if (IC) {  // 16 lanes x one 4x4 SATD (the four 16-lane rows compute the same sum)
+    const int b4 = lane & 15, px = (b4 & 3) * 4, py = (b4 >> 2) * 4;
+    int d[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[i * 4 + j] = res[(py + i) * 16 + px + j];
+    const int sat = row16_sum(satd4(d));
+    if (lane == 0) icost[bo] = sat;
+  }
   const int rnd = inter_rounding((long long)satd_acc[b], W, H);
   int nz = code_tb<4>(res, ta, tb, ti, 0, 0, qidx, rnd, ly + bo * 256);
   for (int i = lane; i < 256; i += 64)
@@ -716,10 +732,14 @@ __device__ void load_edges(const uint8_t* P, int w, int x, int y, int N, EdgeLds
   __syncthreads();
 }
 
-__global__ void __launch_bounds__(64) k_av1e_intra(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
-                                                   uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
-                                                   int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
-                                                   const int* __restrict__ qarr, int diag, int bx_lo) {
+// The intra block coder on the calling wave: block (bx, by) of segment b, mode search on the
+// reconstructed neighbours in rec, residual coding, reconstruction, mode / MV words.  Shared by
+// the key-frame wavefront (k_av1e_intra) and the intra blocks of inter frames
+// (k_av1e_ib_recon); force-inlined so its LDS arrays stay LDS accesses in both.
+__device__ __forceinline__ void intra_code_block(const Planes3& src, const Planes3W& rec, uint32_t* __restrict__ mode,
+                                                 uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
+                                                 int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
+                                                 int qidx, int b, int bx, int by) {
   __shared__ EdgeLds E[2];
   __shared__ uint8_t sblk[256];
   __shared__ uint8_t sc[2][64];
@@ -727,8 +747,8 @@ __global__ void __launch_bounds__(64) k_av1e_intra(Planes3 src, Planes3W rec, ui
   __shared__ int16_t res[256], ta[256], tb[256];
   __shared__ int32_t ti[256];
   __shared__ int predc[256];
-  const int lane = threadIdx.x, b = blockIdx.y, qidx = qarr[b];
-  const int bw = W >> 4, bx = bx_lo + blockIdx.x, by = diag - bx, x0 = bx * 16, y0 = by * 16;
+  const int lane = threadIdx.x;
+  const int bw = W >> 4, x0 = bx * 16, y0 = by * 16;
   const long ysz = (long)W * H, csz = ysz >> 2;
   const int lam = lambda16(qidx), Wc = W >> 1, cx0 = bx * 8, cy0 = by * 8;
   const uint8_t* S = src.y + b * ysz;
@@ -811,6 +831,95 @@ __global__ void __launch_bounds__(64) k_av1e_intra(Planes3 src, Planes3W rec, ui
     mode[bo] = pack_mode(0, ym, uvm, nz == 0, nz);
     mvout[bo] = 0;
   }
+}
+
+__global__ void __launch_bounds__(64) k_av1e_intra(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
+                                                   uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
+                                                   int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
+                                                   const int* __restrict__ qarr, int diag, int bx_lo) {
+  const int b = blockIdx.y, bx = bx_lo + blockIdx.x;
+  intra_code_block(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, bx, diag - bx);
+}
+
+// ================================================== intra blocks in inter frames =========
+// tv/av1_enc.h "intra blocks in inter frames"; all on the stream, counts stay on the device.
+//   k_av1e_ib_analyse  one wave per block: blocks past the gate (icost from k_av1e_inter<1,
+//                      true>) run the seven-mode luma SATD search on SOURCE-neighbour edges in
+//                      the k_av1e_intra lane layout and write the candidate byte;
+//   k_av1e_ib_select   one thread per block: ib_accepted from the candidate map, the map byte
+//                      (bit 0 candidate, bit 1 accepted) and the block appended to its pass's list
+//                      (order within a pass is free: its blocks are independent);
+//   k_av1e_ib_recon    one launch per pass over a fixed grid (at most four blocks of a pass
+//                      per 4x4-block tile): wave i codes list entry i with intra_code_block, waves
+//                      beyond the pass's count return at once.
+__global__ void __launch_bounds__(64) k_av1e_ib_analyse(const uint8_t* __restrict__ srcy, const int* __restrict__ icost,
+                                                        uint8_t* __restrict__ cand, int W, int H,
+                                                        const int* __restrict__ qarr) {
+  __shared__ EdgeLds E;
+  __shared__ uint8_t sblk[256];
+  __shared__ int cost[8];
+  const int lane = threadIdx.x, blk = blockIdx.x, b = blockIdx.y;
+  const int bw = W >> 4, nb = bw * (H >> 4), bx = blk % bw, by = blk / bw, x0 = bx * 16, y0 = by * 16;
+  const long bo = (long)b * nb + blk;
+  const int ic = icost[bo];
+  if (!ib_gated(ic)) {  // wave-uniform
+    if (lane == 0) cand[bo] = 0;
+    return;
+  }
+  const int lam = lambda16(qarr[b]);
+  const uint8_t* S = srcy + (long)b * W * H;
+  for (int i = lane; i < 256; i += 64) sblk[i] = S[(long)(y0 + (i >> 4)) * W + x0 + (i & 15)];
+  load_edges(S, W, x0, y0, 16, E);
+  const int grp = lane >> 4, b4 = lane & 15, px = (b4 & 3) * 4, py = (b4 >> 2) * 4;
+  for (int pass = 0; pass < (kNumIntraCand + 3) / 4; ++pass) {
+    const int ci = pass * 4 + grp;
+    const int m = intra_cand(ci < kNumIntraCand ? ci : 0);
+    int d[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        d[i * 4 + j] = (int)sblk[(py + i) * 16 + px + j] - intra_pred_px(m, E.e, 16, py + i, px + j, E.dc);
+    const int sat = row16_sum(satd4(d));
+    if (b4 == 0 && ci < kNumIntraCand) cost[ci] = sat;
+  }
+  __syncthreads();
+  if (lane == 0) {
+    const int best = ib_best_cost([&](int m) {
+      int k = 0;
+      while (intra_cand(k) != m) ++k;
+      return cost[k];
+    }, lam);
+    cand[bo] = ib_candidate(ic, best, lam) ? 1 : 0;
+  }
+}
+
+// cnt [B][kIbPasses] (zeroed before the launch), list [B][kIbPasses][nb]
+__global__ void k_av1e_ib_select(const uint8_t* __restrict__ cand, uint8_t* __restrict__ ib, int* __restrict__ cnt,
+                                 uint32_t* __restrict__ list, int W, int H) {
+  const int b = blockIdx.y, bw = W >> 4, nb = bw * (H >> 4);
+  const int blk = blockIdx.x * blockDim.x + threadIdx.x;
+  if (blk >= nb) return;
+  const int bx = blk % bw, by = blk / bw;
+  const uint8_t* c = cand + (long)b * nb;
+  const bool acc = ib_accepted(c, bw, bx, by);
+  ib[(long)b * nb + blk] = (uint8_t)((c[blk] & 1) | (acc ? 2 : 0));
+  if (acc) {
+    const int slot = b * kIbPasses + ib_pass(bx, by);
+    const int k = atomicAdd(&cnt[slot], 1);  // < nb: every block is appended at most once
+    list[(long)slot * nb + k] = (uint32_t)blk;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_av1e_ib_recon(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
+                                                      uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
+                                                      int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
+                                                      const int* __restrict__ qarr, const int* __restrict__ cnt,
+                                                      const uint32_t* __restrict__ list, int pass) {
+  const int b = blockIdx.y, bw = W >> 4, nb = bw * (H >> 4), slot = b * kIbPasses + pass;
+  if ((int)blockIdx.x >= min(cnt[slot], nb)) return;  // wave-uniform: beyond the pass's count
+  const int blk = (int)list[(long)slot * nb + blockIdx.x];
+  intra_code_block(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, blk % bw, blk / bw);
 }
 
 // ================================================================= loop-filter info ======
@@ -1096,16 +1205,16 @@ const char* tv_av1e_last_error() { return g_err.c_str(); }
 // device q-index per segment (1..255, range-checked by the host engine).  The motion field
 // goes through `tmp` ([B][nb] words): search -> tmp, kMvRefineRounds refinement rounds
 // ping-ponging between tmp and mv (ending in mv), then the recon at mv.
-int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
-                  const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv, uint32_t* tmp,
-                  unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H,
-                  int B, const int* qarr, void* stream) {
+static int inter_frame(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
+                       const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv,
+                       uint32_t* tmp, unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu,
+                       int16_t* lv, int* icost, int W, int H, int B, const int* qarr, void* stream) {
   if (bad(W, H, B, 1, "av1e_inter") || ensure_tables()) return -1;
   static_assert(kMvRefineRounds % 2 == 1, "an odd round count ends the field in `mv`");
   const int nb = (W >> 4) * (H >> 4), nsb = ((W + 63) >> 6) * ((H + 63) >> 6);
   hipStream_t st = (hipStream_t)stream;
   k_av1e_inter<0><<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov}, mode,
-                                              nullptr, tmp, ly, lu, lv, W, H, qarr, satd_acc);
+                                              nullptr, tmp, ly, lu, lv, W, H, qarr, satd_acc, nullptr);
   // memo: two [B][nb] record sets (mv words, SATDs, counts), ping-ponged across the rounds
   const long nrec = (long)B * nb;
   MvMemo mm[2];
@@ -1123,9 +1232,57 @@ int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const
   }
   if (hipMemsetAsync(satd_acc, 0, (size_t)B * sizeof(unsigned long long), st) != hipSuccess) return status("av1e_inter");
   k_av1e_mv_unify<<<dim3(nsb, B), 256, 0, st>>>(sy, ry, mv, W, H, qarr, satd_acc);
-  k_av1e_inter<1><<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov}, mode,
-                                              mv, mv, ly, lu, lv, W, H, qarr, satd_acc);
+  if (icost)
+    k_av1e_inter<1, true><<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov},
+                                                      mode, mv, mv, ly, lu, lv, W, H, qarr, satd_acc, icost);
+  else
+    k_av1e_inter<1><<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov}, mode,
+                                                mv, mv, ly, lu, lv, W, H, qarr, satd_acc, nullptr);
   return status("av1e_inter");
+}
+
+int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
+                  const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv, uint32_t* tmp,
+                  unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H,
+                  int B, const int* qarr, void* stream) {
+  return inter_frame(sy, su, sv, ry, ru, rv, oy, ou, ov, mode, mv, tmp, satd_acc, memo, ly, lu, lv, nullptr, W, H, B,
+                     qarr, stream);
+}
+
+// tv_av1e_inter that also writes every block's inter cost (luma SATD at its final MV) to
+// icost [B][nb], the input of tv_av1e_iblocks.
+int tv_av1e_inter_cost(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
+                       const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv,
+                       uint32_t* tmp, unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu,
+                       int16_t* lv, int* icost, int W, int H, int B, const int* qarr, void* stream) {
+  if (!icost) {
+    g_err = "av1e_inter_cost: no cost buffer";
+    return -1;
+  }
+  return inter_frame(sy, su, sv, ry, ru, rv, oy, ou, ov, mode, mv, tmp, satd_acc, memo, ly, lu, lv, icost, W, H, B,
+                     qarr, stream);
+}
+
+// Intra blocks of an inter frame (tv/av1_enc.h), between tv_av1e_inter_cost and tv_av1e_merge:
+// o* / mode / mv / l* are the frame's reconstruction and decisions (accepted blocks are
+// overwritten); icost [B][nb] from tv_av1e_inter_cost; scratch cand [B][nb] bytes, cnt
+// [B][7] ints, list [B][7][nb] words; ib [B][nb]: bit 0 candidate, bit 1 accepted.
+int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
+                    uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, const int* icost,
+                    uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B, const int* qarr,
+                    void* stream) {
+  if (bad(W, H, B, 1, "av1e_iblocks") || ensure_tables()) return -1;
+  const int nb = (W >> 4) * (H >> 4);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(cnt, 0, (size_t)B * kIbPasses * sizeof(int), st) != hipSuccess) return status("av1e_iblocks");
+  k_av1e_ib_analyse<<<dim3(nb, B), 64, 0, st>>>(sy, icost, cand, W, H, qarr);
+  k_av1e_ib_select<<<dim3((nb + 255) / 256, B), 256, 0, st>>>(cand, ib, cnt, list, W, H);
+  // a 4x4-block tile has at most 4 blocks of one pass (lx + ly = 3), whole or cut by the frame edge
+  const int gmax = (((W >> 4) + 3) >> 2) * (((H >> 4) + 3) >> 2) * 4;
+  for (int pass = 0; pass < kIbPasses; ++pass)
+    k_av1e_ib_recon<<<dim3(gmax, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov}, mode, mv, ly, lu,
+                                                         lv, W, H, qarr, cnt, list, pass);
+  return status("av1e_iblocks");
 }
 
 // Key frame of B segments: one launch per anti-diagonal of the 16x16 block grid.

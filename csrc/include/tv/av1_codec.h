@@ -64,6 +64,7 @@ struct FrameData {
   std::vector<int16_t> ly, lu, lv;  // full (unpacked) [nblk][256|64]
   std::vector<int8_t> cdef_idx;
   std::vector<int32_t> lr;          // [3][nu_luma][3]
+  std::vector<uint8_t> ib;          // inter frames: [nblk] bit 0 intra candidate, bit 1 accepted (av1_enc.h)
   FrameDecisions view() const;
 };
 
@@ -102,7 +103,9 @@ struct GoldenOut {
   std::vector<FrameData> frames;
   std::vector<Planes> recon;
 };
-GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qindex);
+// qmap (optional): per-frame q-index; tools: coding-tools word (av1_enc.h kToolIntraInInter)
+GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qindex, const int* qmap = nullptr,
+                        int tools = 0);
 
 // CDEF preset choice shared with the GPU kernel: greedy luma presets on the SSE of active
 // 64x64 blocks, per-index chroma preset, joint reassignment.  sse_* [nfb][64].

@@ -14,6 +14,8 @@
 //   * inter frames: one reference (LAST = previous frame), quarter-pel motion, EIGHTTAP
 //     (regular) filters; the NEWMV / NEARESTMV / NEARMV / GLOBALMV choice is made by the
 //     syntax writer from the spatial MV stack (the mode does not change the reconstruction);
+//     opt-in (kToolIntraInInter, off by default): 16x16 intra blocks where the reference has
+//     no match ("intra blocks in inter frames" below);
 //   * deblocking with frame levels, CDEF (8 presets per frame, 64x64 cdef_idx).
 //
 // Every normative table (q lookup, default CDFs) is the specification's (tv/av1_tables.h)
@@ -473,6 +475,100 @@ TV_HD void merge_sb(uint32_t* mode, const uint32_t* mv, int bw, int bh, int sx, 
 TV_HD uint32_t pack_mv(int row, int col) { return (uint32_t)(row & 0xFFFF) | ((uint32_t)(col & 0xFFFF) << 16); }
 TV_HD int mv_row(uint32_t v) { return (int)(int16_t)(v & 0xFFFF); }
 TV_HD int mv_col(uint32_t v) { return (int)(int16_t)(v >> 16); }
+
+// --------------------------------------------------- intra blocks in inter frames -------
+// Opt-in tool (kToolIntraInInter, off by default): 16x16 blocks of an inter frame whose
+// content has no match in the reference (a cut the scene detector missed, uncovered
+// background, motion beyond +-kMeRange) are coded as intra blocks.  The model runs per inter
+// frame once the motion field is final and every block has been coded as inter, before
+// merge_sb.
+//   inter cost   luma 16x16 SATD of the source against the inter prediction at the final MV;
+//   gate         only blocks with inter cost > kIbGate * 256 are analysed;
+//   candidate    the seven intra_cand modes predicted from SOURCE neighbours (intra_edges on
+//                the source frame, so every block is analysed independently), mode cost =
+//                SATD + ((lam * intra_mode_bits16(m)) >> 8), first minimum; the block is a
+//                candidate when ib_cost(best, lam) < inter cost;
+//   acceptance   ib_accepted(): a pure function of the candidate flags of a bounded
+//                neighbourhood (below);
+//   recon        accepted blocks are re-coded exactly as key-frame blocks are (luma and chroma
+//                mode search on RECONSTRUCTED neighbours, kRndIntra, uv_txtype) and overwrite
+//                the block's reconstruction, levels, mode word (pack_mode(0, ym, uvm, skip,
+//                nz), block size 0) and MV word (0).
+// Acceptance is a wavefront local to each 64x64 superblock: with lx = bx & 3, ly = by & 3,
+// block b belongs to pass d = lx + ly (0..6), and pass d of every superblock of the frame
+// runs before pass d + 1.  An intra block reads its left, above and above-left neighbours
+// (no above-right, no below-left sample).  Those inside b's superblock belong to passes d - 1
+// and d - 2: final when b runs.  Those in another superblock have lx = 3 or ly = 3 while b
+// has lx = 0 or ly = 0 there, so they belong to a LATER pass (left of an lx = 0 block: pass
+// 3 + ly > ly; likewise above and above-left); b may only read them if they stay inter, so a
+// candidate is accepted unless one of its outside neighbours is itself accepted.  An outside
+// neighbour of an edge block is either interior (lx > 0 && ly > 0: no outside neighbour,
+// accepted whenever candidate) or an edge block whose own outside neighbours are all
+// interior, so the recursion ends after two steps (ib_accepted<2>).  Blocks on the picture's
+// left / top edge have no neighbour there.
+// Order independence: an accepted block reads only samples that are final when it runs -
+// inter blocks that are never re-coded, and accepted blocks of earlier passes, which are also
+// earlier in raster order.  So re-coding the accepted blocks in raster order (golden encoder,
+// the decoder's order) and in pass order (GPU) gives the same reconstruction by induction.
+// No rule that accepts more and stays a bounded pure function was found: letting an edge
+// block win against its outside neighbour needs a tie-break that propagates along a row
+// of superblocks.
+// Constants: BD-rate of the tool against off with the golden encoder (tools/rd_curve.py --codec
+// av1 --intra-in-inter 1, QP 22..37 = q 60..160; 320x192 x 8 frames with --cut 4 smooth /
+// textured, the same without a cut ("pan"), 640x360 x 16 frames of the bench content smooth /
+// textured; profiles/av1_intra_blocks/README.md):
+//   s * 5/4, gate 4, 16 bits (the start)   -8.79  -3.89   0.00  +0.06  -0.24
+//   s * 3/2, gate 4, 16 bits               -7.34  -2.00   0.00  +0.08  +0.05
+//   s * 5/4, gate 4,  8 bits               -8.99  -4.28   0.00  +0.10  -0.29
+//   s * 5/4, gate 2, 16 bits               -8.79  -3.89   0.00  +0.06  -0.24  (= gate 4)
+//   s * 5/4, gate 8, 16 bits               -8.12  -3.89   0.00  -0.16  -0.24
+//   s * 9/8, gate 4, 24 bits               -8.93  -4.99  -0.06  +0.02  -0.26
+//   s * 1,   gate 4, 32 bits               -9.27  -6.26  -0.62  -0.09  -0.65
+//   s * 1,   gate 4, 16 bits               -9.75  -7.38  -0.54  -0.26  -1.24
+//   s * 1,   gate 4,  8 bits              -10.17  -7.75  -0.80  -1.08  -1.31
+//   s * 7/8, gate 4, 32 bits               -9.97  -8.31  -0.73  -0.54  -1.46
+//   s * 7/8, gate 4, 16 bits (kept)       -10.16  -8.74  -0.21  -0.93  -1.70
+//   s * 3/4, gate 4, 16 bits              -10.43  -9.38  -0.58  -0.83  -1.39
+// Weights below 1 keep gaining although source neighbours flatter the intra SATD; why was not
+// investigated.  The curve is flat between 1 and 3/4; 7/8 is the best on the textured bench
+// content and touches the pan clip least of the three.
+constexpr int kToolIntraInInter = 1;  // bit of the encoders' tools word
+constexpr int kIbGate = 4;            // inter SATD per luma sample below which a block is not analysed
+constexpr int kIbPenBits = 16;
+TV_HD bool ib_gated(int inter_cost) { return inter_cost > kIbGate * 256; }
+TV_HD int ib_cost(int s, int lam) { return s * 7 / 8 + ((lam * kIbPenBits) >> 4); }
+// Luma mode decision of one block from the edges `e` (source neighbours for the analysis):
+// sat(mode) -> 16x16 SATD of the source against the mode's prediction.  Returns the least
+// cost (first minimum over intra_cand order).
+template <class F>
+TV_HD int ib_best_cost(F sat, int lam) {
+  int best = 1 << 30;
+  for (int k = 0; k < kNumIntraCand; ++k) {
+    const int c = sat(intra_cand(k)) + ((lam * intra_mode_bits16(intra_cand(k))) >> 8);
+    if (c < best) best = c;
+  }
+  return best;
+}
+TV_HD bool ib_candidate(int inter_cost, int best_intra, int lam) {
+  return ib_gated(inter_cost) && ib_cost(best_intra, lam) < inter_cost;
+}
+TV_HD int ib_pass(int bx, int by) { return (bx & 3) + (by & 3); }
+constexpr int kIbPasses = 7;
+// cand [bh][bw]: bit 0 = candidate.  D = remaining recursion depth (callers use 2).
+template <int D>
+TV_HD bool ib_accepted_d(const uint8_t* cand, int bw, int bx, int by) {
+  if (!(cand[by * bw + bx] & 1)) return false;
+  if constexpr (D > 0) {
+    for (int k = 0; k < 3; ++k) {  // left, above, above-left
+      const int nx = bx - (k != 1), ny = by - (k != 0);
+      if (nx < 0 || ny < 0) continue;
+      if ((nx >> 2) == (bx >> 2) && (ny >> 2) == (by >> 2)) continue;
+      if (ib_accepted_d<D - 1>(cand, bw, nx, ny)) return false;
+    }
+  }
+  return true;
+}
+TV_HD bool ib_accepted(const uint8_t* cand, int bw, int bx, int by) { return ib_accepted_d<2>(cand, bw, bx, by); }
 
 // deblocking info word for a 4x4 unit (av1_defs.h layout): tx = block = 16 << bsz luma,
 // 8 << bsz chroma

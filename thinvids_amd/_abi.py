@@ -85,6 +85,9 @@ CORE = {
     "tv_av1c_qlookup": (i, [i, i]),
     "tv_av1c_golden_encode": (i, [i, i, i, u8p, i, i32p, vp, i64p, u8p, u32p, u32p, i16p, i16p, i16p, i32p, i8p,
                                   i32p]),
+    "tv_av1c_golden_encode_tools": (i, [i, i, i, u8p, i, i32p, i, vp, i64p, u8p, u32p, u32p, i16p, i16p, i16p, i32p,
+                                        i8p, i32p, u8p]),
+    "tv_av1c_ib_accept": (i, [u8p, i, i, u8p]),
     "tv_av1c_decode": (i, [u8p, sz, i, u8p, i32p, i32p]),
     "tv_av1c_probe": (i, [u8p, sz, i32p, i32p]),
     "tv_av1c_state_new": (vp, []),
@@ -173,6 +176,8 @@ GPU = {
     # k_av1_enc.hip: the AV1 engine (device pointers, stream last)
     "tv_av1e_last_error": (cstr, []),
     "tv_av1e_inter": (i, [vp] * 17 + [i, i, i, vp, vp]),
+    "tv_av1e_inter_cost": (i, [vp] * 18 + [i, i, i, vp, vp]),
+    "tv_av1e_iblocks": (i, [vp] * 16 + [i, i, i, vp, vp]),
     "tv_av1e_intra": (i, [vp] * 11 + [i, i, i, vp, vp]),
     "tv_av1e_cdef_skip": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_merge": (i, [vp, vp, i, i, i, vp]),

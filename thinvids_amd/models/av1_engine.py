@@ -6,6 +6,7 @@ current HIP stream:
 
     key frame   k_av1e_intra (anti-diagonal wavefront of 16x16 blocks)
     P frame     k_av1e_inter (full-pel +-16 LDS search, quarter-pel refine, recon)
+                [intra_in_inter: k_av1e_ib_analyse -> k_av1e_ib_select -> 7 x k_av1e_ib_recon]
     both        k_av1e_lfinfo -> k_deblock (Y, U, V) -> k_cdef_dir -> k_av1e_cdef_skip ->
                 k_cdef_search (Y, U, V) -> k_av1e_cdef_choose -> k_cdef_apply -> next reference
 
@@ -75,14 +76,20 @@ class GopHost:
     key: list            # per frame
     qm: np.ndarray = None  # (F, B) q-index per frame and segment
     lr: np.ndarray = None  # (F, B, 3, nu, 3) restoration units (set | -1, xqd0, xqd1)
+    ib: np.ndarray = None  # (F, B, nb) uint8: bit 0 intra candidate, bit 1 accepted (intra_in_inter engines)
 
 
 class Av1GpuEngine:
     """B segments x one GOP per call on one GPU; see module docstring."""
 
     def __init__(self, width: int, height: int, batch: int, qindex: int = 100, device: int = 0,
-                 threads: int | None = None, cascade: bool = True):
+                 threads: int | None = None, cascade: bool = True, intra_in_inter: bool = False):
+        """`intra_in_inter` (off by default): 16x16 blocks of inter frames may be coded as intra
+        blocks (av1_enc.h "intra blocks in inter frames"; k_av1e_ib_*), as the golden encoder
+        does with the same flag."""
         import torch
+
+        self.intra_in_inter = bool(intra_in_inter)
 
         self.cascade = bool(cascade)  # constant q: the low-delay q cascade (av1.cascade_qmap)
         self.torch = torch
@@ -132,6 +139,7 @@ class Av1GpuEngine:
                 "fbidx": torch.zeros((F, B, nfb), dtype=torch.int8, device=d),
                 "sse": torch.zeros((F, B, 3), dtype=torch.int64, device=d),
                 "lr": torch.zeros((F, B, 3, self.nu, 3), dtype=torch.int32, device=d),
+                **({"ib": torch.zeros((F, B, nb), dtype=torch.uint8, device=d)} if self.intra_in_inter else {}),
             })
         self._slot_busy = [None, None]
         self._slot = 0
@@ -143,7 +151,7 @@ class Av1GpuEngine:
         if self._slot_busy[s] is not None:  # the previous GOP in this slot is still being collected
             self._slot_busy[s].result()
             self._slot_busy[s] = None
-        for n in self._NAMES:
+        for n in self._NAMES + (("ib",) if self.intra_in_inter else ()):
             setattr(self, "g_" + n, self._slots[s][n])
         return s
 
@@ -161,6 +169,8 @@ class Av1GpuEngine:
         mode, mv = self.g_mode[t, :B], self.g_mv[t, :B]
         ly, lu, lv = self.g_ly[t, :B], self.g_lu[t, :B], self.g_lv[t, :B]
         if key:
+            if self.intra_in_inter:
+                self.g_ib[t, :B].zero_()
             _ok(lib.tv_av1e_intra(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly), _p(lu),
                                   _p(lv), W, H, B, _p(qarr), st))
         else:
@@ -169,9 +179,23 @@ class Av1GpuEngine:
                 self._satd = torch.empty(self.B, dtype=torch.int64, device=self.dev)  # per-segment frame SATD
                 # refinement memo: 2 x [B][nb] x (11 MV words + 11 SATDs + a count)
                 self._memo = torch.empty(2 * self.B * self.nb * (11 * 8 + 1), dtype=torch.uint8, device=self.dev)
-            _ok(lib.tv_av1e_inter(_p(sy), _p(su), _p(sv), _p(fy), _p(fu), _p(fv), _p(ry), _p(ru), _p(rv), _p(mode),
-                                  _p(mv), _p(self._mvtmp), _p(self._satd), _p(self._memo), _p(ly), _p(lu), _p(lv), W, H,
-                                  B, _p(qarr), st))
+            if not self.intra_in_inter:
+                _ok(lib.tv_av1e_inter(_p(sy), _p(su), _p(sv), _p(fy), _p(fu), _p(fv), _p(ry), _p(ru), _p(rv),
+                                      _p(mode), _p(mv), _p(self._mvtmp), _p(self._satd), _p(self._memo), _p(ly),
+                                      _p(lu), _p(lv), W, H, B, _p(qarr), st))
+            else:
+                if getattr(self, "_ibcost", None) is None:  # scratch of the intra-block passes, once per engine
+                    n = self.B * self.nb
+                    self._ibcost = torch.empty(n, dtype=torch.int32, device=self.dev)
+                    self._ibcand = torch.empty(n, dtype=torch.uint8, device=self.dev)
+                    self._ibcnt = torch.empty(self.B * 7, dtype=torch.int32, device=self.dev)
+                    self._iblist = torch.empty(7 * n, dtype=torch.int32, device=self.dev)
+                _ok(lib.tv_av1e_inter_cost(_p(sy), _p(su), _p(sv), _p(fy), _p(fu), _p(fv), _p(ry), _p(ru), _p(rv),
+                                           _p(mode), _p(mv), _p(self._mvtmp), _p(self._satd), _p(self._memo), _p(ly),
+                                           _p(lu), _p(lv), _p(self._ibcost), W, H, B, _p(qarr), st))
+                _ok(lib.tv_av1e_iblocks(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly),
+                                        _p(lu), _p(lv), _p(self._ibcost), _p(self._ibcand), _p(self.g_ib[t, :B]),
+                                        _p(self._ibcnt), _p(self._iblist), W, H, B, _p(qarr), st))
             _ok(lib.tv_av1e_merge(_p(mode), _p(mv), W, H, B, st))
         iy = torch.empty((B, H // 4, W // 4), dtype=torch.int32, device=self.dev)
         iu = torch.empty((B, H // 8, W // 8), dtype=torch.int32, device=self.dev)
@@ -316,6 +340,7 @@ class Av1GpuEngine:
                 key=[t == 0 for t in range(F)],
                 qm=qm,
                 lr=S["lr"][:F, :nseg].cpu().numpy(),
+                ib=S["ib"][:F, :nseg].cpu().numpy() if "ib" in S else None,
             )
         return host
 

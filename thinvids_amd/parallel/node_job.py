@@ -1079,6 +1079,8 @@ def main(argv=None) -> int:
                     help="HEVC: sub-pel motion vectors chosen by SATD + MV rate (off by default)")
     ap.add_argument("--sign-hiding", dest="sign_hiding", action="store_true",
                     help="HEVC: sign data hiding (off by default)")
+    ap.add_argument("--av1-intra-blocks", dest="intra_in_inter", action="store_true",
+                    help="AV1: 16x16 intra blocks in inter frames (off by default)")
     ap.add_argument("--deinterlace", action="store_true", help="bwdif every segment (DVD-native interlaced sources)")
     a = ap.parse_args(argv)
     import torch
@@ -1099,7 +1101,8 @@ def main(argv=None) -> int:
                   software=a.software, resume_dir=a.resume_dir, max_retries=a.max_retries, bframes=a.bframes,
                   tools={"wpp": a.wpp, "rqt": a.rqt, "pintra": a.pintra, "cascade": a.cascade, "rdoq": a.rdoq,
                          **({"subpel_satd": True} if a.subpel_satd else {}),
-                         **({"sign_hiding": True} if a.sign_hiding else {})},
+                         **({"sign_hiding": True} if a.sign_hiding else {}),
+                         **({"intra_in_inter": True} if a.intra_in_inter else {})},
                   deinterlace=a.deinterlace)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res), flush=True)

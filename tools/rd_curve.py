@@ -25,6 +25,8 @@ def run_point(args):
     w, h = map(int, a["res"].split("x"))
     seed = a["seed"] | (1 << 31 if a["textured"] else 0)
     frames = [hevc.synth_frame(seed, t, w, h) for t in range(a["frames"])]
+    if a.get("cut"):  # frames from `cut` on come from an unrelated seed and start: a cut inside the GOP
+        frames[a["cut"]:] = [hevc.synth_frame(seed + 16, 40 + t, w, h) for t in range(a["cut"], a["frames"])]
     cascade = a["cascade"]
     fq = None
     if cascade:
@@ -49,7 +51,8 @@ def run_point(args):
             qm = None
             if fq is not None:  # a QP cascade in HEVC QP units, mapped to q-indices
                 qm = [av1.qindex_for_hevc_qp(x) for x in fq[s0:s0 + n]]
-            r = av1.golden_encode(frames[s0:s0 + a["gop"]], w, h, q, qmap=qm)
+            r = av1.golden_encode(frames[s0:s0 + a["gop"]], w, h, q, qmap=qm,
+                                  intra_in_inter=a.get("intra_in_inter", False))
             stream += r.stream
             ys += [hevc.psnr(f[0], rec[:W * H].reshape(H, W)[:h, :w]) for f, rec in zip(frames[s0:], r.recon)]
     else:
@@ -109,6 +112,8 @@ def main():
     ap.add_argument("--rdoq", type=int, default=1, help="RDOQ-lite coefficient-group trimming")
     ap.add_argument("--subpel-satd", type=int, default=0, help="sub-pel vectors chosen by SATD + MV rate (tv/me_model.h)")
     ap.add_argument("--sign-hiding", type=int, default=0, help="sign data hiding (tv/sdh.h)")
+    ap.add_argument("--intra-in-inter", type=int, default=0, help="av1: intra blocks in inter frames (tv/av1_enc.h)")
+    ap.add_argument("--cut", type=int, default=0, help="frames from this index on are unrelated content (a cut that stays a P frame)")
     ap.add_argument("--engine", choices=("cpu", "gpu"), default="cpu", help="gpu: run the points on the GPU engine, one after another")
     ap.add_argument("--anchor", default="")
     ap.add_argument("--out", default="")
@@ -117,7 +122,7 @@ def main():
                cascade=[int(x) for x in a.cascade.split(",")] if a.cascade else [], iqp=a.iqp,
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
                ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
-               sign_hiding=bool(a.sign_hiding),
+               sign_hiding=bool(a.sign_hiding), intra_in_inter=bool(a.intra_in_inter), cut=a.cut,
                engine=a.engine)
     qps = [int(q) for q in a.qps.split(",")]
     if a.engine == "gpu":
