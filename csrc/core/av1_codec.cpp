@@ -115,6 +115,7 @@ typedef uint16_t C17[17];  // up to 16 symbols + adaptation counter
 struct Cdfs {
   C17 partition[4][4];          // [bsl - 1][ctx]: 8x8 (4 syms), 16 / 32 / 64 (10 syms)
   C17 kf_y[5][5], y_mode[4], uv[2][13], angle[8];
+  C17 cfl_sign, cfl_alpha[6];
   C17 skip[3], is_inter[4], single_ref[3][6];
   C17 new_mv[6], zero_mv[2], ref_mv[6], drl[3];
   C17 mv_joint, mv_sign[2], mv_class[2], class0_bit[2], class0_fr[2][2], mv_fr[2], mv_bits[2][10];
@@ -142,6 +143,8 @@ template <class F> void visit_cdfs(Cdfs& c, F f) {
   each(c.uv[0], 13, f);
   each(c.uv[1], 14, f);
   each(c.angle, 7, f);
+  each(c.cfl_sign, 8, f);
+  each(c.cfl_alpha, 16, f);
   each(c.skip, 2, f);
   each(c.is_inter, 2, f);
   each(c.single_ref, 2, f);
@@ -187,6 +190,8 @@ void init_cdfs(Cdfs& c, int qidx) {
   set_cdfs(c.uv[0], kUvMode0[0], 12, 13);
   set_cdfs(c.uv[1], kUvMode1[0], 13, 14);
   set_cdfs(c.angle, kAngleDelta[0], 6, 7);
+  set_cdf(c.cfl_sign, kCflSign, 8);
+  set_cdfs(c.cfl_alpha, kCflAlpha[0], 15, 16);
   set_cdfs(c.skip, kSkip[0], 1, 2);
   set_cdfs(c.is_inter, kIntraInter[0], 1, 2);
   for (int r = 0; r < 3; ++r) set_cdfs(c.single_ref[r], kSingleRef[r][0], 1, 2);
@@ -806,14 +811,36 @@ struct Tile {
       if (ad != 3) throw std::runtime_error("av1 oracle: angle delta outside the encoder subset");
     }
     io.sym(uvm, cdf.uv[1][y], 14);  // CfL allowed for 16x16
-    if (uvm == 13) throw std::runtime_error("av1 oracle: CfL outside the encoder subset");
-    if (directional(uvm)) {
+    int au = 0, av = 0;
+    if (uvm == UV_CFL_PRED) {  // read_cfl_alphas: joint sign, then |alpha| - 1 of each nonzero plane
+      if (IO::kW) {
+        au = mode_cfl_u(mode[b]), av = mode_cfl_v(mode[b]);
+        if ((!au && !av) || std::abs(au) > 16 || std::abs(av) > 16)
+          throw std::runtime_error("av1 writer: CfL block without a codable alpha pair");
+      }
+      auto sgn = [](int a) { return a == 0 ? 0 : (a < 0 ? 1 : 2); };  // CFL_SIGN_ZERO / NEG / POS
+      int joint = sgn(au) * 3 + sgn(av) - 1;
+      io.sym(joint, cdf.cfl_sign, 8);
+      const int su = (joint + 1) / 3, sv = (joint + 1) % 3;
+      int magu = std::abs(au) - 1, magv = std::abs(av) - 1;
+      if (su) {
+        io.sym(magu, cdf.cfl_alpha[(su - 1) * 3 + sv], 16);
+        au = su == 1 ? -(magu + 1) : magu + 1;
+      }
+      if (sv) {
+        io.sym(magv, cdf.cfl_alpha[(sv - 1) * 3 + su], 16);
+        av = sv == 1 ? -(magv + 1) : magv + 1;
+      }
+    } else if (directional(uvm)) {
       int ad = 3;
       io.sym(ad, cdf.angle[uvm - V_PRED], 7);
       if (ad != 3) throw std::runtime_error("av1 oracle: angle delta outside the encoder subset");
     }
     ymode[b] = (uint8_t)y;
-    if (!IO::kW) mode[b] = pack_mode(0, y, uvm, mode_skip(mode[b]), mode_nz(mode[b]));
+    if (!IO::kW) {
+      mode[b] = pack_mode(0, y, uvm, mode_skip(mode[b]), mode_nz(mode[b]));
+      if (uvm == UV_CFL_PRED) mode[b] = with_cfl(mode[b], au, av);
+    }
   }
 
   void inter_modes(int b, int mir, int mic, bool availU, bool availL) {
@@ -1608,6 +1635,13 @@ void predict(const SeqGeo& g, int p, int bx, int by, uint32_t m, uint32_t mvw, c
   IntraEdge e;
   intra_edges(get, x0, y0, N, e);
   const int mode = p ? mode_uv(m) : mode_y(m), dc = intra_dc(e, N);
+  if (p && mode == UV_CFL_PRED) {  // chroma from luma: the block's own luma reconstruction in rec.y
+    int16_t ac[64];
+    cfl_ac_block([&](int x, int y) { return (int)rec.y[(size_t)y * g.W + x]; }, bx * 16, by * 16, ac);
+    const int alpha = p == 1 ? mode_cfl_u(m) : mode_cfl_v(m);
+    for (int i = 0; i < 64; ++i) pred[i] = cfl_pred_px(dc, alpha, ac[i]);
+    return;
+  }
   for (int i = 0; i < N; ++i)
     for (int j = 0; j < N; ++j) pred[i * N + j] = intra_pred_px(mode, e, N, i, j, dc);
 }
@@ -1878,22 +1912,16 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
           for (int i = 0; i < N; ++i)
             for (int j = 0; j < N; ++j) s[p][i * N + j] = P[(size_t)(by * N + i) * w + bx * N + j];
         }
-        int ym = 0, uvm = 0, inter = 0;
+        int ym = 0, uvm = 0, inter = 0, cfl_u = 0, cfl_v = 0;
         uint32_t mvw = 0;
-        if (fd.fp.key || as_intra) {
+        // TV_AV1_DBG bit 32: the search also tries D113 / D135 / D157 (conformance tests of
+        // the directional predictor; the shipped search leaves them out, av1_enc.h)
+        const int ncand = (dbg & 8) ? 1 : kNumIntraCand + ((dbg & 32) ? 3 : 0);
+        auto cand = [](int k) { return k < kNumIntraCand ? intra_cand(k) : D135_PRED + (k - kNumIntraCand); };
+        // chroma decision of an intra block; runs once the block's luma is reconstructed in rec
+        // (chroma from luma reads it; the regular modes read the chroma neighbours only)
+        auto chroma_search = [&] {
           int best = 1 << 30;
-          // TV_AV1_DBG bit 32: the search also tries D113 / D135 / D157 (conformance tests of
-          // the directional predictor; the shipped search leaves them out, av1_enc.h)
-          const int ncand = (dbg & 8) ? 1 : kNumIntraCand + ((dbg & 32) ? 3 : 0);
-          auto cand = [](int k) { return k < kNumIntraCand ? intra_cand(k) : D135_PRED + (k - kNumIntraCand); };
-          for (int k = 0; k < ncand; ++k) {
-            const uint32_t m = pack_mode(0, cand(k), 0, 0, 0);
-            int pr[256];
-            predict(g, 0, bx, by, m, 0, rec, nullptr, pr);
-            const int cost = satd_block(s[0], pr, 16) + ((lam * intra_mode_bits16(cand(k))) >> 8);
-            if (cost < best) best = cost, ym = cand(k), std::memcpy(pred[0], pr, sizeof(pr));
-          }
-          best = 1 << 30;
           for (int k = 0; k < ncand; ++k) {
             const uint32_t m = pack_mode(0, 0, cand(k), 0, 0);
             int pu[64], pv[64];
@@ -1906,6 +1934,40 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
               std::memcpy(pred[1], pu, sizeof(pu));
               std::memcpy(pred[2], pv, sizeof(pv));
             }
+          }
+          if (!(tools & kToolCfl)) return;
+          int16_t ac[64];
+          cfl_ac_block([&](int x, int y) { return (int)rec.y[(size_t)y * g.W + x]; }, bx * 16, by * 16, ac);
+          int den = 0, a0[2], dcv[2], sat[2][3] = {{0, 0, 0}, {0, 0, 0}}, pc[64];
+          for (int i = 0; i < 64; ++i) den += ac[i] * ac[i];
+          for (int pl = 0; pl < 2; ++pl) {
+            predict(g, 1 + pl, bx, by, pack_mode(0, 0, DC_PRED, 0, 0), 0, rec, nullptr, pc);
+            const int dc = dcv[pl] = pc[0];
+            int num = 0;
+            for (int i = 0; i < 64; ++i) num += ac[i] * (s[1 + pl][i] - dc);
+            a0[pl] = cfl_fit(num, den);
+            for (int k = 0; k < 3; ++k) {
+              const int a = cfl_cand(a0[pl], k);
+              if (a < -16 || a > 16) continue;
+              for (int i = 0; i < 64; ++i) pc[i] = cfl_pred_px(dc, a, ac[i]);
+              sat[pl][k] = satd_block(s[1 + pl], pc, 8);
+            }
+          }
+          if (!cfl_decide(a0[0], a0[1], sat[0], sat[1], lam, best, &cfl_u, &cfl_v)) return;
+          uvm = UV_CFL_PRED;
+          for (int pl = 0; pl < 2; ++pl) {
+            const int a = pl ? cfl_v : cfl_u;
+            for (int i = 0; i < 64; ++i) pred[1 + pl][i] = cfl_pred_px(dcv[pl], a, ac[i]);
+          }
+        };
+        if (fd.fp.key || as_intra) {
+          int best = 1 << 30;
+          for (int k = 0; k < ncand; ++k) {
+            const uint32_t m = pack_mode(0, cand(k), 0, 0, 0);
+            int pr[256];
+            predict(g, 0, bx, by, m, 0, rec, nullptr, pr);
+            const int cost = satd_block(s[0], pr, 16) + ((lam * intra_mode_bits16(cand(k))) >> 8);
+            if (cost < best) best = cost, ym = cand(k), std::memcpy(pred[0], pr, sizeof(pr));
           }
         } else if (force_mv) {
           inter = 1;
@@ -1960,6 +2022,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
         int nz = 0;
         for (int p = 0; p < 3; ++p) {
           const int N = p ? 8 : 16, lg = p ? 3 : 4, w = p ? g.W / 2 : g.W;
+          if (p == 1 && !inter) chroma_search();
           const int txt = p == 0 || inter ? 0 : uv_txtype(uvm);
           int16_t* lev = p == 0 ? &fd.ly[(size_t)b * 256] : (p == 1 ? &fd.lu[(size_t)b * 64] : &fd.lv[(size_t)b * 64]);
           if (dbg & 16) {
@@ -1971,6 +2034,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
             for (int j = 0; j < N; ++j) P[(size_t)(by * N + i) * w + bx * N + j] = (uint8_t)rc[i * N + j];
         }
         fd.mode[b] = pack_mode(inter, ym, uvm, nz == 0, nz);
+        if (uvm == UV_CFL_PRED) fd.mode[b] = with_cfl(fd.mode[b], cfl_u, cfl_v);
         fd.mv[b] = inter ? mvw : 0;
     };
     if (fd.fp.key) {  // intra: left / above dependencies (raster order)
@@ -2298,6 +2362,37 @@ int tv_av1c_ib_accept(const uint8_t* cand, int bw, int bh, uint8_t* acc) {
     if (bw < 1 || bh < 1) throw std::runtime_error("av1: bad block grid");
     for (int by = 0; by < bh; ++by)
       for (int bx = 0; bx < bw; ++bx) acc[by * bw + bx] = ib_accepted(cand, bw, bx, by) ? 1 : 0;
+  });
+}
+
+// Chroma-from-luma fit and decision of one block (av1_enc.h "chroma from luma"): luma [256]
+// the block's reconstructed luma, su / sv [64] the chroma sources, dc_u / dc_v the planes'
+// DC_PRED values, best the cost of the best regular mode.  out [9] = den, num_u, num_v, a0_u,
+// a0_v, alpha_u, alpha_v, CfL wins (0 / 1), cfl_bits16(alpha_u, alpha_v).
+int tv_av1c_cfl_decide(const uint8_t* luma, const uint8_t* su, const uint8_t* sv, int dc_u, int dc_v, int lam, int best,
+                       int32_t* out) {
+  return codec_guard([&] {
+    int16_t ac[64];
+    cfl_ac_block([&](int x, int y) { return (int)luma[y * 16 + x]; }, 0, 0, ac);
+    int den = 0, num[2] = {0, 0}, a0[2], sat[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    for (int i = 0; i < 64; ++i) den += ac[i] * ac[i];
+    for (int pl = 0; pl < 2; ++pl) {
+      const uint8_t* s = pl ? sv : su;
+      const int dc = pl ? dc_v : dc_u;
+      int src[64], pr[64];
+      for (int i = 0; i < 64; ++i) src[i] = s[i], num[pl] += ac[i] * (s[i] - dc);
+      a0[pl] = cfl_fit(num[pl], den);
+      for (int k = 0; k < 3; ++k) {
+        const int a = cfl_cand(a0[pl], k);
+        if (a < -16 || a > 16) continue;
+        for (int i = 0; i < 64; ++i) pr[i] = cfl_pred_px(dc, a, ac[i]);
+        sat[pl][k] = satd_block(src, pr, 8);
+      }
+    }
+    int au = 0, av = 0;
+    const bool win = cfl_decide(a0[0], a0[1], sat[0], sat[1], lam, best, &au, &av);
+    const int32_t r[9] = {den, num[0], num[1], a0[0], a0[1], au, av, win ? 1 : 0, cfl_bits16(au, av)};
+    std::memcpy(out, r, sizeof(r));
   });
 }
 

@@ -12,7 +12,9 @@
 //   k_av1e_intra   one wave per 16x16 block of an anti-diagonal (key frames): the seven
 //                  candidate modes read no above-right samples, so the frame is a plain
 //                  (rows + cols - 1)-step wavefront; 4 luma modes x 16 lanes per pass, all
-//                  7 chroma modes x 8 lanes (U + V 4x4 SATDs) in one pass.
+//                  7 chroma modes x 8 lanes (U + V 4x4 SATDs) in one pass.  <true>: the opt-in
+//                  chroma-from-luma instantiation of the block coder (kToolCfl): luma subsample
+//                  from LDS, wave-sum alpha fit, one 24-lane SATD pass over the candidates.
 //   k_av1e_ib_*    opt-in intra blocks of inter frames (tv/av1_enc.h): per-block candidate
 //                  analysis on source neighbours, acceptance + per-pass lists, seven
 //                  list-driven launches of the key-frame block coder.
@@ -736,6 +738,12 @@ __device__ void load_edges(const uint8_t* P, int w, int x, int y, int N, EdgeLds
 // reconstructed neighbours in rec, residual coding, reconstruction, mode / MV words.  Shared by
 // the key-frame wavefront (k_av1e_intra) and the intra blocks of inter frames
 // (k_av1e_ib_recon); force-inlined so its LDS arrays stay LDS accesses in both.
+// CFL (kToolCfl, tv/av1_enc.h "chroma from luma"): lane (i, j) forms L of chroma sample (i, j)
+// from the luma reconstruction still in LDS (predc + res), keeps its ac in a register and in
+// acl[] for the SATD lanes; num / den are wave sums, so the fitted alphas are wave-uniform;
+// one extra SATD pass covers the 2 planes x 3 candidates (24 lanes, one 4x4 each, summed over
+// each quad) and cfl_decide compares the result with the best regular mode.
+template <bool CFL>
 __device__ __forceinline__ void intra_code_block(const Planes3& src, const Planes3W& rec, uint32_t* __restrict__ mode,
                                                  uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
                                                  int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
@@ -747,6 +755,7 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
   __shared__ int16_t res[256], ta[256], tb[256];
   __shared__ int32_t ti[256];
   __shared__ int predc[256];
+  __shared__ int16_t acl[CFL ? 64 : 1];
   const int lane = threadIdx.x;
   const int bw = W >> 4, x0 = bx * 16, y0 = by * 16;
   const long ysz = (long)W * H, csz = ysz >> 2;
@@ -791,6 +800,15 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
   for (int i = lane; i < 256; i += 64)
     RY[(long)(y0 + (i >> 4)) * W + x0 + (i & 15)] = (uint8_t)clip_pixel(predc[i] + res[i]);
   __syncthreads();
+  int ac = 0, den = 0;
+  if constexpr (CFL) {
+    const int k0 = (lane >> 3) * 32 + (lane & 7) * 2;  // luma (2i, 2j) of chroma sample (i, j)
+    auto rl = [&](int k) { return clip_pixel(predc[k] + res[k]); };
+    const int L = cfl_luma(rl(k0), rl(k0 + 1), rl(k0 + 16), rl(k0 + 17));
+    ac = L - cfl_avg(wave_sum(L));
+    acl[lane] = (int16_t)ac;
+    den = wave_sum(ac * ac);
+  }
   // ---- chroma: kNumIntraCand candidates x 8 lanes (U: 4 blocks, V: 4 blocks), 8 per pass
   uint8_t* RU = rec.u + b * csz;
   uint8_t* RV = rec.v + b * csz;
@@ -809,16 +827,40 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
     if (q == 0 && ci < kNumIntraCand) cost[ci] = sat + ((lam * intra_mode_bits16(m)) >> 8);
   }
   __syncthreads();
-  int uvm = intra_cand(0);
-  {
-    int bc = cost[0];
-    for (int k = 1; k < kNumIntraCand; ++k)
-      if (cost[k] < bc) bc = cost[k], uvm = intra_cand(k);
+  int uvm = intra_cand(0), bc = cost[0];
+  for (int k = 1; k < kNumIntraCand; ++k)
+    if (cost[k] < bc) bc = cost[k], uvm = intra_cand(k);
+  int au = 0, av = 0;
+  if constexpr (CFL) {
+    const int a0u = cfl_fit(wave_sum(ac * ((int)sc[0][lane] - E[0].dc)), den);
+    const int a0v = cfl_fit(wave_sum(ac * ((int)sc[1][lane] - E[1].dc)), den);
+    // lane = plane * 12 + candidate * 4 + 4x4 sub-block; costs in cost[8 + plane * 3 + candidate]
+    const int pl = lane >= 12, k = ((lane - pl * 12) >> 2) & 3, qb = lane & 3, qx = (qb & 1) * 4, qy = (qb >> 1) * 4;
+    int sat = 0;
+    if (lane < 24) {
+      const int a = cfl_cand(pl ? a0v : a0u, k), dc = E[pl].dc;
+      int d[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int o = (qy + i) * 8 + qx + j;
+          d[i * 4 + j] = (int)sc[pl][o] - cfl_pred_px(dc, a, acl[o]);
+        }
+      sat = satd4(d);
+    }
+    sat += dpp::mov<dpp::kQuadXor1>(sat);
+    sat += dpp::mov<dpp::kQuadXor2>(sat);
+    if (lane < 24 && qb == 0) cost[8 + pl * 3 + k] = sat;
+    __syncthreads();
+    if (cfl_decide(a0u, a0v, &cost[8], &cost[11], lam, bc, &au, &av)) uvm = UV_CFL_PRED;
   }
   const int txt = uv_txtype(uvm);
   for (int pl = 0; pl < 2; ++pl) {
     __syncthreads();
-    const int p = intra_pred_px(uvm, E[pl].e, 8, lane >> 3, lane & 7, E[pl].dc);
+    int p;
+    if (CFL && uvm == UV_CFL_PRED) p = cfl_pred_px(E[pl].dc, pl ? av : au, ac);
+    else p = intra_pred_px(uvm, E[pl].e, 8, lane >> 3, lane & 7, E[pl].dc);
     predc[lane] = p;
     res[lane] = (int16_t)((int)sc[pl][lane] - p);
     __syncthreads();
@@ -828,17 +870,20 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
     Rw[(long)(cy0 + (lane >> 3)) * Wc + cx0 + (lane & 7)] = (uint8_t)clip_pixel(predc[lane] + res[lane]);
   }
   if (lane == 0) {
-    mode[bo] = pack_mode(0, ym, uvm, nz == 0, nz);
+    uint32_t m = pack_mode(0, ym, uvm, nz == 0, nz);
+    if (CFL && uvm == UV_CFL_PRED) m = with_cfl(m, au, av);
+    mode[bo] = m;
     mvout[bo] = 0;
   }
 }
 
+template <bool CFL>
 __global__ void __launch_bounds__(64) k_av1e_intra(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
                                                    uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
                                                    int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
                                                    const int* __restrict__ qarr, int diag, int bx_lo) {
   const int b = blockIdx.y, bx = bx_lo + blockIdx.x;
-  intra_code_block(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, bx, diag - bx);
+  intra_code_block<CFL>(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, bx, diag - bx);
 }
 
 // ================================================== intra blocks in inter frames =========
@@ -911,6 +956,7 @@ __global__ void k_av1e_ib_select(const uint8_t* __restrict__ cand, uint8_t* __re
   }
 }
 
+template <bool CFL>
 __global__ void __launch_bounds__(64) k_av1e_ib_recon(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
                                                       uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
                                                       int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
@@ -919,7 +965,7 @@ __global__ void __launch_bounds__(64) k_av1e_ib_recon(Planes3 src, Planes3W rec,
   const int b = blockIdx.y, bw = W >> 4, nb = bw * (H >> 4), slot = b * kIbPasses + pass;
   if ((int)blockIdx.x >= min(cnt[slot], nb)) return;  // wave-uniform: beyond the pass's count
   const int blk = (int)list[(long)slot * nb + blockIdx.x];
-  intra_code_block(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, blk % bw, blk / bw);
+  intra_code_block<CFL>(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, blk % bw, blk / bw);
 }
 
 // ================================================================= loop-filter info ======
@@ -1267,10 +1313,11 @@ int tv_av1e_inter_cost(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, 
 // o* / mode / mv / l* are the frame's reconstruction and decisions (accepted blocks are
 // overwritten); icost [B][nb] from tv_av1e_inter_cost; scratch cand [B][nb] bytes, cnt
 // [B][7] ints, list [B][7][nb] words; ib [B][nb]: bit 0 candidate, bit 1 accepted.
-int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
-                    uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, const int* icost,
-                    uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B, const int* qarr,
-                    void* stream) {
+// tools: the coding-tools word (kToolCfl: the accepted blocks also try chroma from luma).
+int tv_av1e_iblocks_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou,
+                          uint8_t* ov, uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv,
+                          const int* icost, uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B,
+                          const int* qarr, int tools, void* stream) {
   if (bad(W, H, B, 1, "av1e_iblocks") || ensure_tables()) return -1;
   const int nb = (W >> 4) * (H >> 4);
   hipStream_t st = (hipStream_t)stream;
@@ -1279,24 +1326,39 @@ int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uin
   k_av1e_ib_select<<<dim3((nb + 255) / 256, B), 256, 0, st>>>(cand, ib, cnt, list, W, H);
   // a 4x4-block tile has at most 4 blocks of one pass (lx + ly = 3), whole or cut by the frame edge
   const int gmax = (((W >> 4) + 3) >> 2) * (((H >> 4) + 3) >> 2) * 4;
+  const auto recon = (tools & kToolCfl) ? k_av1e_ib_recon<true> : k_av1e_ib_recon<false>;
   for (int pass = 0; pass < kIbPasses; ++pass)
-    k_av1e_ib_recon<<<dim3(gmax, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov}, mode, mv, ly, lu,
-                                                         lv, W, H, qarr, cnt, list, pass);
+    recon<<<dim3(gmax, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov}, mode, mv, ly, lu, lv, W, H, qarr,
+                                        cnt, list, pass);
   return status("av1e_iblocks");
+}
+int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
+                    uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, const int* icost,
+                    uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B, const int* qarr,
+                    void* stream) {
+  return tv_av1e_iblocks_tools(sy, su, sv, oy, ou, ov, mode, mv, ly, lu, lv, icost, cand, ib, cnt, list, W, H, B, qarr,
+                               0, stream);
 }
 
 // Key frame of B segments: one launch per anti-diagonal of the 16x16 block grid.
+// tools: the coding-tools word (kToolCfl: every block also tries chroma from luma).
+int tv_av1e_intra_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
+                        uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H, int B,
+                        const int* qarr, int tools, void* stream) {
+  if (bad(W, H, B, 1, "av1e_intra") || ensure_tables()) return -1;
+  const int bw = W >> 4, bh = H >> 4;
+  const auto intra = (tools & kToolCfl) ? k_av1e_intra<true> : k_av1e_intra<false>;
+  for (int d = 0; d < bw + bh - 1; ++d) {
+    const int lo = d - (bh - 1) > 0 ? d - (bh - 1) : 0, hi = d < bw - 1 ? d : bw - 1;
+    intra<<<dim3(hi - lo + 1, B), 64, 0, (hipStream_t)stream>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov}, mode, mv,
+                                                                ly, lu, lv, W, H, qarr, d, lo);
+  }
+  return status("av1e_intra");
+}
 int tv_av1e_intra(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
                   uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H, int B,
                   const int* qarr, void* stream) {
-  if (bad(W, H, B, 1, "av1e_intra") || ensure_tables()) return -1;
-  const int bw = W >> 4, bh = H >> 4;
-  for (int d = 0; d < bw + bh - 1; ++d) {
-    const int lo = d - (bh - 1) > 0 ? d - (bh - 1) : 0, hi = d < bw - 1 ? d : bw - 1;
-    k_av1e_intra<<<dim3(hi - lo + 1, B), 64, 0, (hipStream_t)stream>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov},
-                                                                       mode, mv, ly, lu, lv, W, H, qarr, d, lo);
-  }
-  return status("av1e_intra");
+  return tv_av1e_intra_tools(sy, su, sv, oy, ou, ov, mode, mv, ly, lu, lv, W, H, B, qarr, 0, stream);
 }
 
 // flag the 8x8 blocks of skip blocks in dir [B][n8] (after tv_gpu_cdef_dirs)

@@ -10,7 +10,9 @@
 //   * key frames: intra modes DC / V / H / SMOOTH / SMOOTH_V / SMOOTH_H / PAETH searched (D113 /
 //     D135 / D157 predicted and decodable too); all read no above-right / below-left samples,
 //     so the I-frame wavefront is a plain diagonal; angle delta 0; intra edge filter / filter
-//     intra / CfL / palette off;
+//     intra / palette off; opt-in (kToolCfl, off by default): chroma from luma as an eighth
+//     chroma mode of every intra block ("chroma from luma" below), which reads only the
+//     block's own reconstructed luma, so the wavefront is unchanged;
 //   * inter frames: one reference (LAST = previous frame), quarter-pel motion, EIGHTTAP
 //     (regular) filters; the NEWMV / NEARESTMV / NEARMV / GLOBALMV choice is made by the
 //     syntax writer from the spatial MV stack (the mode does not change the reconstruction);
@@ -58,7 +60,7 @@ TV_HD int uv_txtype(int uv_mode) {
     case V_PRED: case D113_PRED: case SMOOTH_V_PRED: return 1;      // ADST_DCT
     case H_PRED: case D157_PRED: case SMOOTH_H_PRED: return 2;      // DCT_ADST
     case D135_PRED: case SMOOTH_PRED: case PAETH_PRED: return 3;    // ADST_ADST
-    default: return 0;                                      // DCT_DCT
+    default: return 0;                                      // DCT_DCT (DC_PRED, UV_CFL_PRED)
   }
 }
 
@@ -569,6 +571,103 @@ TV_HD bool ib_accepted_d(const uint8_t* cand, int bw, int bx, int by) {
   return true;
 }
 TV_HD bool ib_accepted(const uint8_t* cand, int bw, int bx, int by) { return ib_accepted_d<2>(cand, bw, bx, by); }
+
+// ------------------------------------------------------------- chroma from luma ---------
+// Opt-in tool (kToolCfl, off by default): UV_CFL_PRED as an eighth chroma mode of every intra
+// block (key frames and the intra blocks of inter frames).  4:2:0, 8x8 chroma of a 16x16 luma
+// block; the coded size is a multiple of 16, so every luma sample of the block is in the frame.
+//   prediction  L[i][j] = (the four reconstructed - before deblocking - luma samples at rows
+//               2i..2i+1, cols 2j..2j+1, summed) << 1; avg = (sum of L + 32) >> 6; ac = L - avg
+//               (|ac| <= 2040); pred = clip_pixel(dc + Round2Signed(alpha * ac, 6)) with dc the
+//               plane's DC_PRED value (intra_dc, missing-neighbour variants included) and
+//               alpha in -16..16 (eighths); transform type DCT_DCT (uv_txtype).
+//   decision    per plane, r = src - dc: num = sum ac * r, den = sum ac^2 (int32; 64 * num in 64
+//               bits), a0 = cfl_fit(num, den); candidates a0, a0 - 1, a0 + 1 inside -16..16,
+//               cost = 8x8 SATD + alpha rate, first strict minimum in that order (cfl_pick);
+//               both alphas zero cannot be signalled: no candidate.  CfL is compared last
+//               against the best of the seven regular modes and wins only when strictly
+//               cheaper (cfl_decide), so every tie keeps the regular mode.
+//   mode word   uv mode 13, alpha_u + 16 in bits 15-20, alpha_v + 16 in bits 21-26 (zero for
+//               every other block).
+// No specification text was at hand: the above (AV1 7.11.5, the cfl_alpha_signs / cfl_alpha_u
+// / cfl_alpha_v syntax and contexts in av1_codec.cpp) is written from memory and dav1d is the
+// arbiter - where dav1d and this description disagree, dav1d wins (tests/test_av1_cfl.py
+// decodes CfL streams with dav1d sample for sample).
+// Rate constants (1/16 bit, the units of intra_mode_bits16; cfl_bits16 = mode + plane(alpha_u) +
+// plane(alpha_v), plane(0) = zero, plane(a) = base + step * (|a| - 1)): BD-rate of the tool
+// against off with the golden encoder (tools/rd_curve.py --codec av1 --cfl 1, QP 22..37, PSNR-Y /
+// 6:1:1 PSNR-YUV; 640x360: 8 frames with chroma = 128 + k/8 (Y2x2 - 128) + noise, k = 6 / -5
+// ("corr"), 16 frames of the bench content smooth / textured at GOP 64, 4 key frames of the
+// same; profiles/av1_cfl/README.md):
+//   mode zero base step    corr           smooth       textured     key smooth   key textured
+//   40   16   40   8 (kept) -17.36/-25.14  +0.24/+0.12  +0.12/+0.11  -0.29/-0.37  -0.00/+0.01
+//   72   16   48   8        -16.65/-24.01  +0.26/+0.16  +0.13/+0.14  -0.32/-0.38  -0.01/+0.00
+//   24   16   32   8        -17.40/-25.44  +0.27/+0.13  +0.12/+0.12  -0.31/-0.39  -0.03/-0.02
+//   56   16   48   8        -17.02/-24.49  +0.26/+0.16  +0.14/+0.14  -0.31/-0.38  -0.00/+0.01
+//   40    8   24   8        -17.45/-25.47  +0.34/+0.21  +0.12/+0.12  -0.30/-0.38  -0.03/-0.02
+// Flat in the constants; the start has the best bench-content figures.  The bench content's
+// chroma does not follow its luma (0.2 % of its key-frame blocks take CfL) and the tool loses
+// 0.1 .. 0.25 % there at GOP 64, which is one reason it ships off.
+constexpr int kToolCfl = 2;  // bit of the encoders' tools word
+constexpr int UV_CFL_PRED = 13;
+constexpr int kCflModeBits16 = 40, kCflZeroBits16 = 16, kCflAlphaBits16 = 40, kCflAlphaStep16 = 8;
+TV_HD int cfl_alpha_bits16(int a) { return a ? kCflAlphaBits16 + kCflAlphaStep16 * (tv_abs(a) - 1) : kCflZeroBits16; }
+TV_HD int cfl_bits16(int au, int av) { return kCflModeBits16 + cfl_alpha_bits16(au) + cfl_alpha_bits16(av); }
+TV_HD uint32_t with_cfl(uint32_t m, int au, int av) {
+  return (m & 0x7FFFu) | ((uint32_t)(au + 16) << 15) | ((uint32_t)(av + 16) << 21);
+}
+TV_HD int mode_cfl_u(uint32_t m) { return (int)((m >> 15) & 63) - 16; }
+TV_HD int mode_cfl_v(uint32_t m) { return (int)((m >> 21) & 63) - 16; }
+// L of one chroma sample from its four luma samples; avg of the block from the sum of its 64 L
+TV_HD int cfl_luma(int a, int b, int c, int d) { return (a + b + c + d) << 1; }
+TV_HD int cfl_avg(int sum) { return (sum + 32) >> 6; }
+TV_HD int cfl_pred_px(int dc, int alpha, int ac) {
+  const int s = alpha * ac;  // Round2Signed(s, 6): the magnitude is rounded, the sign kept
+  return clip_pixel(dc + (s < 0 ? -((-s + 32) >> 6) : (s + 32) >> 6));
+}
+// ac[64] (row-major) of the block whose luma origin is (x0, y0); get(x, y) reads reconstructed luma
+template <class G>
+TV_HD void cfl_ac_block(G get, int x0, int y0, int16_t* ac) {
+  int sum = 0;
+  for (int i = 0; i < 8; ++i)
+    for (int j = 0; j < 8; ++j) {
+      const int x = x0 + 2 * j, y = y0 + 2 * i;
+      const int l = cfl_luma(get(x, y), get(x + 1, y), get(x, y + 1), get(x + 1, y + 1));
+      ac[i * 8 + j] = (int16_t)l;
+      sum += l;
+    }
+  const int avg = cfl_avg(sum);
+  for (int i = 0; i < 64; ++i) ac[i] = (int16_t)(ac[i] - avg);
+}
+// least-squares alpha of one plane in eighths: 64 * num / den rounded to nearest, halves away
+// from zero, clamped to the coded range; 0 for a flat luma block
+TV_HD int cfl_fit(int num, int den) {
+  if (!den) return 0;
+  const long long n = 64LL * num, d = den;
+  const long long q = n >= 0 ? (2 * n + d) / (2 * d) : -((-2 * n + d) / (2 * d));
+  return (int)clip3(-16LL, 16LL, q);
+}
+TV_HD int cfl_cand(int a0, int k) { return k == 0 ? a0 : (k == 1 ? a0 - 1 : a0 + 1); }
+// alpha of one plane from the 8x8 SATDs sat3[k] of its candidates cfl_cand(a0, k); *sat = the
+// chosen candidate's SATD
+TV_HD int cfl_pick(int a0, const int* sat3, int lam, int* sat) {
+  int best = 1 << 30, ba = 0;
+  for (int k = 0; k < 3; ++k) {
+    const int a = cfl_cand(a0, k);
+    if (a < -16 || a > 16) continue;
+    const int c = sat3[k] + ((lam * cfl_alpha_bits16(a)) >> 8);
+    if (c < best) best = c, ba = a, *sat = sat3[k];
+  }
+  return ba;
+}
+// The block's chroma decision: true when CfL beats `best`, the cost of the best regular mode
+TV_HD bool cfl_decide(int a0u, int a0v, const int* satu3, const int* satv3, int lam, int best, int* au, int* av) {
+  int su = 0, sv = 0;
+  *au = cfl_pick(a0u, satu3, lam, &su);
+  *av = cfl_pick(a0v, satv3, lam, &sv);
+  if (!*au && !*av) return false;
+  return su + sv + ((lam * cfl_bits16(*au, *av)) >> 8) < best;
+}
 
 // deblocking info word for a 4x4 unit (av1_defs.h layout): tx = block = 16 << bsz luma,
 // 8 << bsz chroma

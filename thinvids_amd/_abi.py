@@ -88,6 +88,7 @@ CORE = {
     "tv_av1c_golden_encode_tools": (i, [i, i, i, u8p, i, i32p, i, vp, i64p, u8p, u32p, u32p, i16p, i16p, i16p, i32p,
                                         i8p, i32p, u8p]),
     "tv_av1c_ib_accept": (i, [u8p, i, i, u8p]),
+    "tv_av1c_cfl_decide": (i, [u8p, u8p, u8p, i, i, i, i, i32p]),
     "tv_av1c_decode": (i, [u8p, sz, i, u8p, i32p, i32p]),
     "tv_av1c_probe": (i, [u8p, sz, i32p, i32p]),
     "tv_av1c_state_new": (vp, []),
@@ -178,7 +179,9 @@ GPU = {
     "tv_av1e_inter": (i, [vp] * 17 + [i, i, i, vp, vp]),
     "tv_av1e_inter_cost": (i, [vp] * 18 + [i, i, i, vp, vp]),
     "tv_av1e_iblocks": (i, [vp] * 16 + [i, i, i, vp, vp]),
+    "tv_av1e_iblocks_tools": (i, [vp] * 16 + [i, i, i, vp, i, vp]),
     "tv_av1e_intra": (i, [vp] * 11 + [i, i, i, vp, vp]),
+    "tv_av1e_intra_tools": (i, [vp] * 11 + [i, i, i, vp, i, vp]),
     "tv_av1e_cdef_skip": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_merge": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_tb_len": (i, [vp, vp, l, i, i, i, i, vp, vp]),

@@ -7,6 +7,8 @@ current HIP stream:
     key frame   k_av1e_intra (anti-diagonal wavefront of 16x16 blocks)
     P frame     k_av1e_inter (full-pel +-16 LDS search, quarter-pel refine, recon)
                 [intra_in_inter: k_av1e_ib_analyse -> k_av1e_ib_select -> 7 x k_av1e_ib_recon]
+                [cfl: the <true> instantiations of k_av1e_intra / k_av1e_ib_recon, whose block
+                 coder also tries chroma from luma]
     both        k_av1e_lfinfo -> k_deblock (Y, U, V) -> k_cdef_dir -> k_av1e_cdef_skip ->
                 k_cdef_search (Y, U, V) -> k_av1e_cdef_choose -> k_cdef_apply -> next reference
 
@@ -83,13 +85,17 @@ class Av1GpuEngine:
     """B segments x one GOP per call on one GPU; see module docstring."""
 
     def __init__(self, width: int, height: int, batch: int, qindex: int = 100, device: int = 0,
-                 threads: int | None = None, cascade: bool = True, intra_in_inter: bool = False):
+                 threads: int | None = None, cascade: bool = True, intra_in_inter: bool = False,
+                 cfl: bool = False):
         """`intra_in_inter` (off by default): 16x16 blocks of inter frames may be coded as intra
         blocks (av1_enc.h "intra blocks in inter frames"; k_av1e_ib_*), as the golden encoder
-        does with the same flag."""
+        does with the same flag.  `cfl` (off by default): intra blocks may predict chroma from
+        their reconstructed luma (av1_enc.h "chroma from luma"; k_av1e_intra<true> /
+        k_av1e_ib_recon<true>)."""
         import torch
 
         self.intra_in_inter = bool(intra_in_inter)
+        self.cfl = bool(cfl)
 
         self.cascade = bool(cascade)  # constant q: the low-delay q cascade (av1.cascade_qmap)
         self.torch = torch
@@ -171,8 +177,12 @@ class Av1GpuEngine:
         if key:
             if self.intra_in_inter:
                 self.g_ib[t, :B].zero_()
-            _ok(lib.tv_av1e_intra(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly), _p(lu),
-                                  _p(lv), W, H, B, _p(qarr), st))
+            if self.cfl:
+                _ok(lib.tv_av1e_intra_tools(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly),
+                                            _p(lu), _p(lv), W, H, B, _p(qarr), av1m.TOOL_CFL, st))
+            else:
+                _ok(lib.tv_av1e_intra(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly),
+                                      _p(lu), _p(lv), W, H, B, _p(qarr), st))
         else:
             if getattr(self, "_mvtmp", None) is None:
                 self._mvtmp = torch.empty(self.B * self.nb, dtype=torch.int32, device=self.dev)
@@ -193,9 +203,10 @@ class Av1GpuEngine:
                 _ok(lib.tv_av1e_inter_cost(_p(sy), _p(su), _p(sv), _p(fy), _p(fu), _p(fv), _p(ry), _p(ru), _p(rv),
                                            _p(mode), _p(mv), _p(self._mvtmp), _p(self._satd), _p(self._memo), _p(ly),
                                            _p(lu), _p(lv), _p(self._ibcost), W, H, B, _p(qarr), st))
-                _ok(lib.tv_av1e_iblocks(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly),
-                                        _p(lu), _p(lv), _p(self._ibcost), _p(self._ibcand), _p(self.g_ib[t, :B]),
-                                        _p(self._ibcnt), _p(self._iblist), W, H, B, _p(qarr), st))
+                _ok(lib.tv_av1e_iblocks_tools(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv),
+                                              _p(ly), _p(lu), _p(lv), _p(self._ibcost), _p(self._ibcand),
+                                              _p(self.g_ib[t, :B]), _p(self._ibcnt), _p(self._iblist), W, H, B,
+                                              _p(qarr), av1m.TOOL_CFL if self.cfl else 0, st))
             _ok(lib.tv_av1e_merge(_p(mode), _p(mv), W, H, B, st))
         iy = torch.empty((B, H // 4, W // 4), dtype=torch.int32, device=self.dev)
         iu = torch.empty((B, H // 8, W // 8), dtype=torch.int32, device=self.dev)

@@ -1081,6 +1081,8 @@ def main(argv=None) -> int:
                     help="HEVC: sign data hiding (off by default)")
     ap.add_argument("--av1-intra-blocks", dest="intra_in_inter", action="store_true",
                     help="AV1: 16x16 intra blocks in inter frames (off by default)")
+    ap.add_argument("--av1-cfl", dest="cfl", action="store_true",
+                    help="AV1: chroma from luma in intra blocks (off by default)")
     ap.add_argument("--deinterlace", action="store_true", help="bwdif every segment (DVD-native interlaced sources)")
     a = ap.parse_args(argv)
     import torch
@@ -1102,7 +1104,8 @@ def main(argv=None) -> int:
                   tools={"wpp": a.wpp, "rqt": a.rqt, "pintra": a.pintra, "cascade": a.cascade, "rdoq": a.rdoq,
                          **({"subpel_satd": True} if a.subpel_satd else {}),
                          **({"sign_hiding": True} if a.sign_hiding else {}),
-                         **({"intra_in_inter": True} if a.intra_in_inter else {})},
+                         **({"intra_in_inter": True} if a.intra_in_inter else {}),
+                         **({"cfl": True} if a.cfl else {})},
                   deinterlace=a.deinterlace)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res), flush=True)

@@ -149,7 +149,14 @@ uv1 = aom_table("uv_mode_cfl_allowed", [10407, 11208, 12900, 13181, 13823, 14175
 T["uv_mode0"] = ((13,), 13, uv0)
 T["uv_mode1"] = ((13,), 14, uv1)
 T["angle_delta"] = ((8,), 7, aom_table("angle_delta", [2180, 5032, 7567, 22776, 26989, 30217], 8, 8, 7))
-part = aom_table("partition", [19132, 25510, 30392], 20, 11, lambda k: 4 if k < 4 else (10 if k < 16 else 8))
+# chroma from luma: cfl_alpha_signs (8 joint signs; libaom's encoder image lacks the table,
+# dav1d holds it), cfl_alpha [ctx 6] (|alpha| - 1, 16 symbols; both libraries)
+T["cfl_sign"] = ((), 8, dav1d_table("cfl_sign", [1418, 2123, 13340, 18405, 26972, 28343, 32294],
+                                    [1418, 2123, 13340, 18405, 26972, 28343, 32294], 1, 8))
+T["cfl_alpha"] = ((6,), 16, aom_table("cfl_alpha", [7637, 20719, 31401, 32481], 6, 17, 16))
+if dav1d_table("cfl_alpha", T["cfl_alpha"][2][0], T["cfl_alpha"][2][1], 6, 16) != T["cfl_alpha"][2]:
+    raise SystemExit("cfl_alpha: libaom and dav1d differ")
+part = aom_table("partition",[19132, 25510, 30392], 20, 11, lambda k: 4 if k < 4 else (10 if k < 16 else 8))
 T["partition"] = ((20,), 10, part)
 # intra_ext_tx [set 0..2][txSzSqr 4][mode 13], CDF_SIZE(16) = 17; set 0 is all zero
 s1 = aom_table("intra_ext_tx_set1", [1535, 8035, 9461, 12751, 23467, 27825], 52, 17, 7)

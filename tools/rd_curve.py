@@ -27,6 +27,11 @@ def run_point(args):
     frames = [hevc.synth_frame(seed, t, w, h) for t in range(a["frames"])]
     if a.get("cut"):  # frames from `cut` on come from an unrelated seed and start: a cut inside the GOP
         frames[a["cut"]:] = [hevc.synth_frame(seed + 16, 40 + t, w, h) for t in range(a["cut"], a["frames"])]
+    if a.get("chroma_k"):  # chroma that follows luma (av1.correlated_chroma), e.g. for --cfl
+        from thinvids_amd.models import av1 as _av1
+
+        ku, kv = a["chroma_k"]
+        frames = [_av1.correlated_chroma(f[0], ku, kv, seed=a["seed"] * 1000 + t) for t, f in enumerate(frames)]
     cascade = a["cascade"]
     fq = None
     if cascade:
@@ -36,6 +41,7 @@ def run_point(args):
             fq.append(max(0, min(51, qp + (a["iqp"] if idr else cascade[(i % a["gop"] - 1) % len(cascade)]))))
     import numpy as np
 
+    uv_mse = []
     kw = dict(sao=a["sao"], rqt=a["rqt"], pintra=a["pintra"], wpp=a["wpp"], cascade=a["ippp_cascade"], rdoq=a["rdoq"],
               subpel_satd=a["subpel_satd"], sign_hiding=a.get("sign_hiding", False))
     if a.get("engine") == "gpu":
@@ -52,9 +58,12 @@ def run_point(args):
             if fq is not None:  # a QP cascade in HEVC QP units, mapped to q-indices
                 qm = [av1.qindex_for_hevc_qp(x) for x in fq[s0:s0 + n]]
             r = av1.golden_encode(frames[s0:s0 + a["gop"]], w, h, q, qmap=qm,
-                                  intra_in_inter=a.get("intra_in_inter", False))
+                                  intra_in_inter=a.get("intra_in_inter", False), cfl=a.get("cfl", False))
             stream += r.stream
             ys += [hevc.psnr(f[0], rec[:W * H].reshape(H, W)[:h, :w]) for f, rec in zip(frames[s0:], r.recon)]
+            for f, rec in zip(frames[s0:], r.recon):  # chroma MSE for the 6:1:1 PSNR-YUV
+                c = rec[W * H:].reshape(2, H // 2, W // 2)[:, :(h + 1) // 2, :(w + 1) // 2].astype(np.float64)
+                uv_mse.append([float(np.mean((c[k] - f[1 + k]) ** 2)) for k in range(2)])
     else:
         stream, recons = hevc.encode_sequence_cpu(frames, qp=qp, gop=a["gop"], frame_qps=fq, bframes=a["bframes"], **kw)
         ys = [hevc.psnr(f[0], r[0][:h, :w]) for f, r in zip(frames, recons)]
@@ -62,7 +71,11 @@ def run_point(args):
     mse_y = np.mean([10 ** (-p / 10) for p in ys])
     py = -10 * np.log10(mse_y)
     kbps = len(stream) * 8 * 30 / len(frames) / 1000
-    return {"qp": qp, "kbps": round(kbps, 2), "psnr_y": round(float(py), 4), "frames": len(frames)}
+    pt = {"qp": qp, "kbps": round(kbps, 2), "psnr_y": round(float(py), 4), "frames": len(frames)}
+    if uv_mse:  # av1: PSNR of the 6:1:1 weighted MSE (chroma tools move chroma quality, not luma)
+        mu, mv = np.mean(uv_mse, axis=0) / 255.0 ** 2
+        pt["psnr_yuv"] = round(float(-10 * np.log10(max((6 * mse_y + mu + mv) / 8, 1e-12))), 4)
+    return pt
 
 
 def run_point_gpu(qp, a, w, h, seed, fq, kw):
@@ -113,6 +126,10 @@ def main():
     ap.add_argument("--subpel-satd", type=int, default=0, help="sub-pel vectors chosen by SATD + MV rate (tv/me_model.h)")
     ap.add_argument("--sign-hiding", type=int, default=0, help="sign data hiding (tv/sdh.h)")
     ap.add_argument("--intra-in-inter", type=int, default=0, help="av1: intra blocks in inter frames (tv/av1_enc.h)")
+    ap.add_argument("--cfl", type=int, default=0, help="av1: chroma from luma (tv/av1_enc.h)")
+    ap.add_argument("--chroma-k", default="", help="KU,KV: replace the clip's chroma by one that follows its luma "
+                    "(U = 128 + KU * (Y2x2 - 128) / 8 + noise; models/av1.py correlated_chroma)")
+    ap.add_argument("--metric", choices=("y", "yuv"), default="y", help="BD-rate on PSNR-Y or (av1) on the 6:1:1 PSNR-YUV")
     ap.add_argument("--cut", type=int, default=0, help="frames from this index on are unrelated content (a cut that stays a P frame)")
     ap.add_argument("--engine", choices=("cpu", "gpu"), default="cpu", help="gpu: run the points on the GPU engine, one after another")
     ap.add_argument("--anchor", default="")
@@ -123,7 +140,7 @@ def main():
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
                ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
                sign_hiding=bool(a.sign_hiding), intra_in_inter=bool(a.intra_in_inter), cut=a.cut,
-               engine=a.engine)
+               engine=a.engine, cfl=bool(a.cfl), chroma_k=[int(x) for x in a.chroma_k.split(",")] if a.chroma_k else [])
     qps = [int(q) for q in a.qps.split(",")]
     if a.engine == "gpu":
         pts = [run_point((q, cfg)) for q in qps]
@@ -140,8 +157,9 @@ def main():
 
         with open(a.anchor) as f:
             anc = json.load(f)
-        print(json.dumps({"bd_rate_pct": round(bd_rate([p["kbps"] for p in anc], [p["psnr_y"] for p in anc],
-                                                        [p["kbps"] for p in pts], [p["psnr_y"] for p in pts]), 2)}))
+        m = "psnr_yuv" if a.metric == "yuv" else "psnr_y"
+        print(json.dumps({"bd_rate_pct": round(bd_rate([p["kbps"] for p in anc], [p[m] for p in anc],
+                                                        [p["kbps"] for p in pts], [p[m] for p in pts]), 2), "metric": m}))
 
 
 if __name__ == "__main__":
