@@ -65,7 +65,7 @@ void* tv_cpu_encoder_new(int width, int height, int qp, int deblock, int range, 
   cfg.width = width;
   cfg.height = height;
   cfg.qp = qp;
-  cfg.set_flags(deblock);  // 1 deblocking, 2 SAO, 4 WPP, 8 no RQT, 16 no intra-in-P, ... (SeqConfig::set_flags)
+  cfg.set_flags(deblock);  // the kFlag* bits (tv/hevc_codec.h)
   cfg.max_merge_cand = max_merge;
   cfg.finalize();
   CpuEncoder* e = nullptr;  // a bad config becomes tv_last_error, not an abort across the FFI
@@ -167,7 +167,7 @@ void tv_cpu_encoder_levels(void* e, int16_t* cy, int16_t* cu, int16_t* cv) {
 // ---------------------------- decisions -> reconstruction / bitstream ---------------------
 // Reconstruct a frame from externally supplied decisions (golden model for the GPU).
 // src/ref/rec planes are coded size. coef planes are outputs.  ref may be null for intra.
-// `deblock`: non-zero = deblocking; bit 512 (SeqConfig::set_flags) sign data hiding.
+// `deblock`: non-zero = deblocking; kFlagSignHiding: sign data hiding.
 int tv_reconstruct_frame(int width, int height, int qp, int deblock, const uint8_t* src_y,
                          const uint8_t* src_u, const uint8_t* src_v, const uint8_t* ref_y,
                          const uint8_t* ref_u, const uint8_t* ref_v, const uint8_t* cu_log2,
@@ -179,8 +179,8 @@ int tv_reconstruct_frame(int width, int height, int qp, int deblock, const uint8
     cfg.width = width;
     cfg.height = height;
     cfg.qp = qp;
-    cfg.deblock = (deblock & ~512) != 0;
-    cfg.sign_hiding = (deblock & 512) != 0;
+    cfg.deblock = (deblock & ~kFlagSignHiding) != 0;
+    cfg.sign_hiding = (deblock & kFlagSignHiding) != 0;
     cfg.rqt = false;  // no transform splits (tv_write_frame codes every split flag as 0)
     cfg.finalize();
     const int W = cfg.coded_w, H = cfg.coded_h;
@@ -214,7 +214,7 @@ int tv_reconstruct_frame(int width, int height, int qp, int deblock, const uint8
 }
 
 // Write parameter sets (if idr) + a slice NAL from decision arrays (`deblock` as above: with
-// bit 512 the level planes must satisfy the hidden signs' parity, else this fails).
+// kFlagSignHiding the level planes must satisfy the hidden signs' parity, else this fails).
 int tv_write_frame(int width, int height, int qp, int deblock, int max_merge, int idr, int poc,
                    const uint8_t* cu_log2, const uint8_t* intra, const uint8_t* ipm,
                    const int16_t* mv, const uint8_t* cbf, const int16_t* cy, const int16_t* cu,
@@ -224,8 +224,8 @@ int tv_write_frame(int width, int height, int qp, int deblock, int max_merge, in
     cfg.width = width;
     cfg.height = height;
     cfg.qp = qp;
-    cfg.deblock = (deblock & ~512) != 0;
-    cfg.sign_hiding = (deblock & 512) != 0;
+    cfg.deblock = (deblock & ~kFlagSignHiding) != 0;
+    cfg.sign_hiding = (deblock & kFlagSignHiding) != 0;
     cfg.max_merge_cand = max_merge;
     cfg.finalize();  // no tu plane: inter CUs code split_transform_flag 0
     FrameData f;

@@ -165,191 +165,185 @@ class ThreadPool {
 };
 
 struct EngineCfg {
-  int width, height, qp, batch, gop, range, deblock, threads, device, max_merge;
+  int width, height, qp, batch, gop, range, flags, threads, device, max_merge;  // flags: tv::kFlag*
   uint32_t seed;
   int groups;
   int crf;  // > 0: in-engine CRF (per-frame QP from the lookahead, tv/rc_model.h)
   int mgop = 1;  // hierarchical-B mini-GOP (tv/gop.h); 1 = I P P P
 };
 
-// One group of segments on its own HIP stream (buffers, pinned slot ring, events).
-class Core {
-  size_t dev_bytes_ = 0, host_bytes_ = 0;
-  template <class T> void dev_alloc(T** p, size_t n) {
-    HIP_OK(hipMalloc(p, n));
-    dev_bytes_ += n;
+// Owns what it hands out and keeps the byte ledger (the engine's HBM footprint).  Count-only:
+// hands out null and only keeps the ledger, so the code that allocates a Core's buffers is
+// also the code that estimates them.
+class Arena {
+ public:
+  explicit Arena(bool count_only) : count_only_(count_only) {}
+  Arena(const Arena&) = delete;
+  ~Arena() {
+    for (void* p : dev_) (void)hipFree(p);
+    for (void* p : host_) (void)hipHostFree(p);
   }
-  template <class T> void host_alloc(T** p, size_t n) {
-    HIP_OK(hipHostMalloc(p, n, hipHostMallocDefault));
-    host_bytes_ += n;
+  template <class T = uint8_t> T* dev(size_t bytes) {
+    dev_bytes_ += bytes;
+    if (count_only_) return nullptr;
+    dev_.push_back(nullptr);
+    HIP_OK(hipMalloc(&dev_.back(), bytes));
+    return static_cast<T*>(dev_.back());
+  }
+  template <class T = uint8_t> T* host(size_t bytes) {
+    host_bytes_ += bytes;
+    if (count_only_) return nullptr;
+    host_.push_back(nullptr);
+    HIP_OK(hipHostMalloc(&host_.back(), bytes, hipHostMallocDefault));
+    return static_cast<T*>(host_.back());
+  }
+  bool count_only() const { return count_only_; }
+  size_t dev_bytes() const { return dev_bytes_; }
+  size_t host_bytes() const { return host_bytes_; }
+
+ private:
+  const bool count_only_;
+  size_t dev_bytes_ = 0, host_bytes_ = 0;
+  std::vector<void*> dev_, host_;
+};
+
+// Successive 256-byte-aligned regions of one block: take() names each region once, size() is
+// where they end (what to allocate), bind() points every named pointer into the block.
+class Carve {
+ public:
+  template <class T> void take(T*& p, size_t bytes) {
+    pack(p, bytes);
+    off_ = (off_ + 255) & ~(size_t)255;
+  }
+  // no padding behind the region: the next one follows at once
+  template <class T> void pack(T*& p, size_t bytes) {
+    at_.push_back({&p, off_});
+    off_ += bytes;
+  }
+  size_t size() const { return off_; }
+  void bind(uint8_t* base) const {  // a null base (count-only arena) leaves the pointers null
+    for (const auto& a : at_) {
+      uint8_t* p = base ? base + a.second : nullptr;
+      std::memcpy(a.first, &p, sizeof p);  // a.first is a T** for some object type T
+    }
   }
 
+ private:
+  size_t off_ = 0;
+  std::vector<std::pair<void*, size_t>> at_;
+};
+
+// a stream / an event destroyed with its owner (also when the owner's constructor throws)
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  void create(unsigned flags) { HIP_OK(hipEventCreateWithFlags(&e, flags)); }
+  operator hipEvent_t() const { return e; }
+};
+
+// One group of segments on its own HIP stream (buffers, pinned slot ring, events).
+class Core {
  public:
-  Core(const EngineCfg& c, ThreadPool* pool) : cfg_(c), g_(make_geo(c.width, c.height)), pool_(pool) {
+  // count_only: validate and lay the buffers out against a counting arena; no device is touched
+  Core(const EngineCfg& c, ThreadPool* pool, bool count_only = false)
+      : cfg_(c), g_(make_geo(c.width, c.height)), mem_(count_only), pool_(pool) {
+    // every check before the first allocation or stream
     if (c.batch < 1 || c.batch > kMaxBatch) throw std::runtime_error("batch must be 1..64");
     if (c.range < 16 || c.range > 128 || (c.range & 15))
       throw std::runtime_error("search range must be a multiple of 16 in 16..128");
     if ((c.width & 1) || (c.height & 1)) throw std::runtime_error("odd frame size");
     if (c.width < 64 || c.height < 64) throw std::runtime_error("frame must be at least 64x64");
-    HIP_OK(hipSetDevice(c.device));
-    fetch_ = std::make_unique<ThreadPool>(1, c.device);
-    HIP_OK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    {  // I-frame wavefront stream: highest priority, so its 100+ short dependent launches are
-       // dispatched ahead of the other stream group's queued P-frame workgroups
-      int lo = 0, hi = 0;
-      HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      HIP_OK(hipStreamCreateWithPriority(&istream_, hipStreamNonBlocking, hi));
-      HIP_OK(hipEventCreateWithFlags(&iev_[0], hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&iev_[1], hipEventDisableTiming));
-    }
-    const long B = c.batch;
-    nctu_ = g_.wc * g_.hc;
-    // bit 2: WPP substreams, bit 3: no RQT, bit 4: no intra-in-P, bit 5: CABAC on the host
-    // (WPP streams are entropy-coded on the GPU unless bit 5 asks for the host writer)
-    gpu_ent_ = gpu_entropy(c);
-    if (gpu_ent_) HIP_OK(hipEventCreateWithFlags(&eev_, hipEventDisableTiming));  // estream_: init_entropy_stream()
-    auto alloc_set = [&](FrameSet& f) {
-      dev_alloc(&f.y, B * g_.ysz);
-      dev_alloc(&f.u, B * g_.csz);
-      dev_alloc(&f.v, B * g_.csz);
-    };
-    alloc_set(src_);
-    // Decoded picture buffer (tv/gop.h): every picture is reconstructed into a free DPB entry
-    // that keeps its final (deblocked + SAO) samples, the 16 quarter-pel phase planes of its
-    // luma (only when a later picture references it) and its quarter-res source luma (the
-    // coarse search's reference); an entry is free again once no later picture needs it.
-    // I P P P needs 2 entries, hierarchical-B mini-GOPs of M frames log2(M) + 2.  With SAO
-    // one scratch set holds the deblocked picture the filter reads.
     if (c.mgop < 1 || c.mgop > 32 || (c.mgop & (c.mgop - 1))) throw std::runtime_error("bframes must be a power of 2 <= 32");
     if (c.mgop > 1 && c.crf > 0) throw std::runtime_error("in-engine CRF is not supported with B frames");
-    ndpb_ = c.mgop > 1 ? plan_gop(2 * c.mgop + 1, c.mgop).dpb_size : 2;
-    if (ndpb_ > kMaxDpb) throw std::runtime_error("DPB too large");
-    qsz_ = (long)(g_.W / 4) * (g_.H / 4);
-    for (int k = 0; k < ndpb_; ++k) {
-      alloc_set(dpb_[k].rec);
-      dev_alloc(&dpb_[k].phase, B * 16 * g_.psz);
-      dev_alloc(&dpb_[k].q, B * qsz_);
-    }
-    if (c.deblock & 2) alloc_set(deb_);
-    dev_alloc(&coef_y_, B * g_.ysz * sizeof(int16_t));
-    dev_alloc(&coef_u_, B * g_.csz * sizeof(int16_t));
-    dev_alloc(&coef_v_, B * g_.csz * sizeof(int16_t));
-    dev_alloc(&d_sse_, B * 3 * sizeof(unsigned long long));
-    dev_alloc(&count_scratch_, B * nctu_ * sizeof(int));
-    // hierarchical motion search: coarse field (+ cost) per list; B pictures: per-list fine
-    // search results for the bi decision
-    dev_alloc(&cmv_, 2 * B * nctu_ * 2 * sizeof(int16_t));
-    dev_alloc(&ccost_, 2 * B * nctu_ * sizeof(int));
-    if (c.mgop > 1) dev_alloc(&meout_, 2 * B * nctu_ * sizeof(CtbMeOut));
-    if (!(c.deblock & 16)) {  // intra-in-P scores and lists (tv/me_model.h pintra_*)
-      uint8_t* m = nullptr;
-      dev_alloc(&m, pintra_bytes(B, nctu_));
-      const long n = B * nctu_;
-      pi_.qcost = reinterpret_cast<int*>(m);
-      pi_.gate = reinterpret_cast<int*>(m + align(n * 16));
-      pi_.pass = reinterpret_cast<int*>(m + 2 * align(n * 16));
-      pi_.clist = reinterpret_cast<int*>(m + 3 * align(n * 16));
-      pi_.count = reinterpret_cast<int*>(m + 4 * align(n * 16));
-      pi_.cand = m + 4 * align(n * 16) + 256;
-    }
-    cap_ = g_.ysz + 2 * g_.csz;
-    // per-slot device + pinned host buffers: decisions | masks | offsets | totals | packed |
-    // entropy head | entropy payload (device only: it lands in the host slot's packed region)
-    slot_bytes(B, g_, gpu_ent_, slot_bytes_, slot_host_bytes_);
-    if (gpu_ent_) {  // per-lane entropy scratch (each lane's stream codes one picture at a time)
-      tok_cap_ = tok_capacity(B, g_);
-      EntropyTables* t = nullptr;
-      dev_alloc(&t, sizeof(EntropyTables));
-      std::unique_ptr<EntropyTables> ht(new EntropyTables());
-      entropy_tables(*ht);
-      HIP_OK(hipMemcpy(t, ht.get(), sizeof(EntropyTables), hipMemcpyHostToDevice));
-      for (int l = 0; l < ent_lanes(); ++l) {  // one allocation carved like ent_core_bytes()
-        EntScratch& e = ent_[l];
-        uint8_t* q = nullptr;
-        dev_alloc(&q, ent_core_bytes(B, g_));
-        e.base = q;
-        e.regions = reinterpret_cast<uint32_t*>(q);
-        q += align(B * nctu_ * kEntRegion * 4);
-        e.tokens = reinterpret_cast<uint32_t*>(q);
-        q += align((tok_cap_ + kTokPad) * 4);
-        e.stage = q;
-        q += align(3 * tok_cap_ + 20 * B * g_.hc + 16);
-        e.ctb_cnt = reinterpret_cast<int*>(q);
-        q += align(B * nctu_ * 4);
-        e.ctb_off = reinterpret_cast<int*>(q);
-        q += align(B * nctu_ * 4);
-        e.seg_tok = reinterpret_cast<int*>(q);
-        q += align(B * 4);
-        e.wflag = reinterpret_cast<int*>(q);
-        q += align(B * g_.hc * 4);
-        e.wctx = q;
-        dev_alloc(&e.skip, B * g_.usz);
-        dev_alloc(&e.midx, B * g_.usz);
-        e.tab = t;
-      }
-      const char* dbg = getenv("TV_ENT_DEBUG");
-      if (dbg && *dbg == '1') {
-        dev_alloc(&ent_dbg_, 8 * sizeof(unsigned long long));
-        HIP_OK(hipMemset(ent_dbg_, 0, 8 * sizeof(unsigned long long)));
-      }
-    }
-    host_alloc(&qhost_, (size_t)c.gop * B);
-    host_alloc(&quni_, (size_t)B);
-    std::memset(quni_, c.qp, (size_t)B);
-    nslots_ = slot_count();
-    slots_.reset(new Slot[nslots_]);
-    for (int k = 0; k < nslots_; ++k) {
-      Slot& s = slots_[k];
-      dev_alloc(&s.dev, slot_bytes_);
-      host_alloc(&s.host, slot_host_bytes_);
-      // waited on by the fetch thread: see sync_mode()
-      HIP_OK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming | (sync_mode() == 2 ? hipEventBlockingSync : 0)));
-
-      s.pending = 0;
-    }
-    HIP_OK(hipEventCreate(&t0_));
-    HIP_OK(hipEventCreate(&t1_));
-    // decision constants of every QP (rate control picks the QP per segment and frame on the
-    // device): identical integer rounding to the CPU reference encoder
-    {
-      RcTables t{};
-      for (int q = 0; q < 52; ++q) {
-        const double lam = lambda_sad(q);
-        Penalties& p = t.pen[q];
-        p.mode_dcpl = (int)(lam * 2);
-        p.mode_ang = (int)(lam * 5);
-        p.split_intra = (int)(lam * 3);
-        p.split_inter = (int)(lam * 4);
-        p.pintra = (int)(lam * kPIntraPenBits);
-        for (int i = 0; i < 64; ++i) p.mv[i] = (int)(lam * i);
-        t.sao_lam16[q] = sao_lambda16(q);
-      }
-      dev_alloc(&rc_, sizeof(RcTables));
-      HIP_OK(hipMemcpy(rc_, &t, sizeof(RcTables), hipMemcpyHostToDevice));
-    }
     seq_.width = c.width;
     seq_.height = c.height;
     seq_.qp = c.qp;
-    seq_.deblock = (c.deblock & 1) != 0;  // bit 0: deblocking, bit 1: SAO
-    seq_.sao = (c.deblock & 2) != 0;
     seq_.max_merge_cand = c.max_merge;
-    seq_.wpp = (c.deblock & 4) != 0;
-    seq_.rqt = !(c.deblock & 8);
-    seq_.pintra = !(c.deblock & 16);
-    seq_.cascade = (c.deblock & 64) != 0;
-    seq_.rdoq = !(c.deblock & 128);
+    seq_.set_flags(c.flags);
     g_.rdoq = seq_.rdoq ? kRdoqMode : 0;
-    seq_.subpel_satd = (c.deblock & 256) != 0;
     g_.subpel_satd = seq_.subpel_satd ? 1 : 0;
-    seq_.sign_hiding = (c.deblock & 512) != 0;
     g_.sign_hiding = seq_.sign_hiding ? 1 : 0;
     seq_.mgop = c.mgop;
     if (c.mgop > 1) {
       const GopPlan gp = plan_gop(2 * c.mgop + 1, c.mgop);
       seq_.dpb_size = gp.dpb_size;
       seq_.num_reorder = gp.num_reorder;
+      ndpb_ = gp.dpb_size;
     }
+    if (ndpb_ > kMaxDpb) throw std::runtime_error("DPB too large");
     seq_.finalize();
+    nctu_ = g_.wc * g_.hc;
+    cap_ = g_.ysz + 2 * g_.csz;
+    // WPP streams are entropy-coded on the GPU (k_entropy.hip) unless the host writer is asked
+    // for, given a geometry the coder handles (>= 2 CTB columns for the 9.3.2.4 storage after
+    // CTB 1, <= 256 rows and columns): anything else uses the host writer from the start
+    gpu_ent_ = seq_.wpp && !(c.flags & kFlagHostEntropy) && g_.wc >= 2 && g_.wc <= 256 && g_.hc <= 256;
+    nslots_ = slot_count();
+    slots_.reset(new Slot[nslots_]);
+    if (count_only) {
+      layout();
+      return;
+    }
+    HIP_OK(hipSetDevice(c.device));
+    fetch_ = std::make_unique<ThreadPool>(1, c.device);
+    HIP_OK(hipStreamCreateWithFlags(&stream_.s, hipStreamNonBlocking));
+    {  // I-frame wavefront stream: highest priority, so its 100+ short dependent launches are
+       // dispatched ahead of the other stream group's queued P-frame workgroups
+      int lo = 0, hi = 0;
+      HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+      HIP_OK(hipStreamCreateWithPriority(&istream_.s, hipStreamNonBlocking, hi));
+      iev_[0].create(hipEventDisableTiming);
+      iev_[1].create(hipEventDisableTiming);
+    }
+    if (gpu_ent_) eev_.create(hipEventDisableTiming);  // estream_: init_entropy_stream()
+    layout();
+    for (int k = 0; k < nslots_; ++k) {
+      Slot& s = slots_[k];
+      // waited on by the fetch thread: see sync_mode()
+      s.ev.create(hipEventDisableTiming | (sync_mode() == 2 ? hipEventBlockingSync : 0));
+      if (gpu_ent_) {  // the pack kernel's destination (pinned, device-visible)
+        HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.hhead), s.h.ent_head, 0));
+        HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.hqp), s.h.qp, 0));
+        HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.hout), s.h.packed, 0));
+      }
+    }
+    t0_.create(hipEventDefault);
+    t1_.create(hipEventDefault);
+    std::memset(quni_, c.qp, (size_t)c.batch);
+    if (ent_dbg_) HIP_OK(hipMemset(ent_dbg_, 0, 8 * sizeof(unsigned long long)));
+    if (gpu_ent_) {
+      std::unique_ptr<EntropyTables> ht(new EntropyTables());
+      entropy_tables(*ht);
+      HIP_OK(hipMemcpy(ent_tab_, ht.get(), sizeof(EntropyTables), hipMemcpyHostToDevice));
+    }
+    // decision constants of every QP (rate control picks the QP per segment and frame on the
+    // device): identical integer rounding to the CPU reference encoder
+    RcTables t{};
+    for (int q = 0; q < 52; ++q) {
+      const double lam = lambda_sad(q);
+      Penalties& p = t.pen[q];
+      p.mode_dcpl = (int)(lam * 2);
+      p.mode_ang = (int)(lam * 5);
+      p.split_intra = (int)(lam * 3);
+      p.split_inter = (int)(lam * 4);
+      p.pintra = (int)(lam * kPIntraPenBits);
+      for (int i = 0; i < 64; ++i) p.mv[i] = (int)(lam * i);
+      t.sao_lam16[q] = sao_lambda16(q);
+    }
+    HIP_OK(hipMemcpy(rc_, &t, sizeof(RcTables), hipMemcpyHostToDevice));
   }
 
   // The core's entropy stream, created by the Engine after every core's main stream: HIP
@@ -362,34 +356,20 @@ class Core {
   // each; creating core 0's two lanes before core 1's put core 1's lane 0 on its main
   // stream's queue and cost 30 % at 1080p)
   void init_entropy_stream(int l) {
-    if (l < ent_lanes()) init_entropy_lane(estream_[l]);
-  }
-  void init_entropy_lane(hipStream_t& estream_) {
-    if (gpu_ent_ && !estream_) HIP_OK(hipStreamCreateWithFlags(&estream_, hipStreamNonBlocking));
+    if (gpu_ent_ && l < ent_lanes() && !estream_[l])
+      HIP_OK(hipStreamCreateWithFlags(&estream_[l].s, hipStreamNonBlocking));
   }
 
   // device / pinned-host bytes this group allocated (the engine's HBM footprint)
-  size_t dev_bytes() const { return dev_bytes_; }
-  size_t host_bytes() const { return host_bytes_; }
+  size_t dev_bytes() const { return mem_.dev_bytes(); }
+  size_t host_bytes() const { return mem_.host_bytes(); }
 
-  // The same byte counts computed without allocating anything (EngineCache budgets and
-  // auto-batch sizing decide before building an engine).  Mirrors the constructor above,
-  // term by term; tests/test_hbm_budget.py checks estimate == footprint on the GPU.
+  // The same byte counts without allocating anything (EngineCache budgets and auto-batch
+  // sizing decide before building an engine): layout() against a counting arena.
   static void estimate(const EngineCfg& c, size_t& dev, size_t& host) {
-    const Geo g = make_geo(c.width, c.height);
-    const size_t B = (size_t)c.batch, nctu = (size_t)g.wc * g.hc, set = B * (g.ysz + 2 * g.csz);
-    const int ndpb = c.mgop > 1 ? plan_gop(2 * c.mgop + 1, c.mgop).dpb_size : 2;
-    const size_t qsz = (size_t)(g.W / 4) * (g.H / 4);
-    const bool ge = gpu_entropy(c);
-    long slot = 0, slot_host = 0;
-    slot_bytes((long)B, g, ge, slot, slot_host);
-    const size_t ent = ge ? env_lanes() * (2 * B * g.usz + ent_core_bytes((long)B, g)) + sizeof(EntropyTables) : 0;
-    dev = set + ndpb * (set + B * 16 * g.psz + B * qsz) + ((c.deblock & 2) ? set : 0) + 2 * set +
-          B * 3 * sizeof(unsigned long long) + B * nctu * sizeof(int) + 2 * B * nctu * 2 * sizeof(int16_t) +
-          2 * B * nctu * sizeof(int) + (c.mgop > 1 ? 2 * B * nctu * sizeof(CtbMeOut) : 0) +
-          (!(c.deblock & 16) ? pintra_bytes((long)B, (long)nctu) : 0) + (size_t)slot_count() * slot +
-          sizeof(RcTables) + ent;
-    host = (size_t)c.gop * B + B + (size_t)slot_count() * slot_host;
+    const Core core(c, nullptr, true);
+    dev = core.dev_bytes();
+    host = core.host_bytes();
   }
 
   ~Core() {
@@ -402,45 +382,9 @@ class Core {
       fprintf(stderr, "[tv entropy] rows %llu: ctx bins/row %.0f, tokens/row %.0f, clocks/ctx bin %.1f, "
               "wait us/row %.1f, coding us/row %.1f, max row span us %.1f\n", h[0], h[1] / n, h[2] / n,
               h[1] ? (double)h[3] / h[1] : 0.0, h[4] / n / 100.0, h[3] / n / 2400.0, h[5] / 100.0);
-      (void)hipFree(ent_dbg_);
     }
-    (void)hipStreamSynchronize(stream_);
-    for (auto* p : {src_.y, src_.u, src_.v, deb_.y, deb_.u, deb_.v}) (void)hipFree(p);
-    for (int k = 0; k < ndpb_; ++k)
-      for (auto* p : {dpb_[k].rec.y, dpb_[k].rec.u, dpb_[k].rec.v, dpb_[k].phase, dpb_[k].q}) (void)hipFree(p);
-    (void)hipFree(meout_);
-    (void)hipFree(pi_.qcost);
-    (void)hipFree(coef_y_);
-    (void)hipFree(coef_u_);
-    (void)hipFree(coef_v_);
-    (void)hipFree(d_sse_);
-    (void)hipFree(count_scratch_);
-    (void)hipFree(cmv_);
-    (void)hipFree(ccost_);
-    (void)hipFree(rc_);
-    if (ent_[0].tab) (void)hipFree(ent_[0].tab);
-    for (const EntScratch& e : ent_)
-      for (void* p : {(void*)e.skip, (void*)e.midx, (void*)e.base}) (void)hipFree(p);
-    (void)hipHostFree(qhost_);
-    (void)hipHostFree(quni_);
-    for (int k = 0; k < nslots_; ++k) {
-      Slot& s = slots_[k];
-      (void)hipFree(s.dev);
-      (void)hipHostFree(s.host);
-      (void)hipEventDestroy(s.ev);
-
-    }
-    (void)hipEventDestroy(t0_);
-    (void)hipEventDestroy(t1_);
-    (void)hipStreamDestroy(stream_);
-    (void)hipEventDestroy(iev_[0]);
-    (void)hipEventDestroy(iev_[1]);
-    (void)hipStreamDestroy(istream_);
-    for (hipStream_t es : estream_)
-      if (es) (void)hipStreamDestroy(es);
-
-    if (dstream_) (void)hipStreamDestroy(dstream_);
-    if (eev_) (void)hipEventDestroy(eev_);
+    if (stream_) (void)hipStreamSynchronize(stream_);
+    // then the members, last declared first: slot events, the arena's memory, events, streams
   }
 
   const std::vector<uint8_t>& segment(int b) const { return out_.at(b); }
@@ -472,108 +416,139 @@ class Core {
     }();
     return n;
   }
-  static long align(long n) { return (n + 255) & ~255L; }
-  // WPP streams are entropy-coded on the GPU (k_entropy.hip) unless bit 5 asks for the host
-  // WPP on, not forced to the host, and a geometry the coder handles (>= 2 CTB columns for the
-  // 9.3.2.4 storage after CTB 1, <= 256 rows and columns): anything else uses the host writer from the start
-  static bool gpu_entropy(const EngineCfg& c) {
-    if (!((c.deblock & 4) && !(c.deblock & 32))) return false;
-    const Geo g = make_geo(c.width, c.height);
-    return g.wc >= 2 && g.wc <= 256 && g.hc <= 256;
-  }
-  // token capacity of the per-core entropy scratch: one token per luma sample of every
-  // segment (the bench's textured I pictures use about a third of that); a picture that
-  // needs more is coded by the host writer instead (status != 0)
-  static long tok_capacity(long B, const Geo& g) {
-    const char* e = getenv("TV_ENT_TOKENS_PER_PX");  // read per engine (tests shrink it)
-    const double per = e ? atof(e) : 1.0;  // textured I pictures at QP 22 use more than 0.5
-    return (long)(per * B * g.ysz) + 1024;
-  }
-  static constexpr long kTokPad = 64;
-  static constexpr long kEntRegion = kEntRegionTokens;
-  // head of the entropy outputs: status, seg_bytes[B], row_bytes[B][hc]
-  static long ent_head_bytes(long B, const Geo& g) { return 16 + 4 * B + 4 * B * g.hc; }
-  static void slot_bytes(long B, const Geo& g, bool ge, long& dev, long& host) {
-    const long nctu = (long)g.wc * g.hc, cap = g.ysz + 2 * g.csz;
-    host = align(B * g.usz) + align(B * g.usz * 4) + align(B * nctu * 8) + align(B * nctu * 4) + align(B * nctu * 4) +
-           align(B * 4) + align(B * nctu * 12) + align(B) + align(B * g.usz) + align(B * g.usz * 4) +
-           align(B * g.usz * 5) + align(B * cap * 2) + (ge ? align(ent_head_bytes(B, g)) : 0);
-    // (the GPU entropy payload goes straight into the host slot's `packed` region)
-    dev = host;
-  }
-  // per-core entropy scratch (the entropy stream codes one picture at a time): CTB token
-  // regions of the single binarisation pass, the picture's contiguous token lists, CTB offsets,
-  // segment totals, coder output staging and the rows' WPP hand-off
-  static long ent_core_bytes(long B, const Geo& g) {
-    const long cap = tok_capacity(B, g), nctu = (long)g.wc * g.hc;
-    return align(B * nctu * kEntRegion * 4) + align((cap + kTokPad) * 4) + align(3 * cap + 20 * B * g.hc + 16) +
-           2 * align(B * nctu * 4) + align(B * 4) + align(B * g.hc * 4) + align(B * g.hc * kEntCtx);
-  }
-  // qcost, gate list, pass lists, candidate list (16 bytes per CTB each), counters, candidate bytes
-  static size_t pintra_bytes(long B, long nctu) { return 4 * align(B * nctu * 16) + 256 + align(B * nctu * 4); }
+  // one slot buffer (device or pinned host) carved into its arrays
+  struct Parts {
+    uint8_t *flags = nullptr, *cu_log2 = nullptr, *intra = nullptr, *ipm = nullptr, *cbf = nullptr, *dir = nullptr,
+            *tu = nullptr;
+    int16_t *mv = nullptr, *mv1 = nullptr;
+    unsigned long long* mask_y = nullptr;
+    unsigned* mask_c = nullptr;
+    int *offset = nullptr, *total = nullptr;
+    int16_t* packed = nullptr;
+    uint32_t* sao = nullptr;
+    int8_t* qp = nullptr;
+    int* ent_head = nullptr;  // GPU entropy: status, seg_bytes[B], row_bytes[B][hc]
+  };
   struct Slot {
-    uint8_t* dev = nullptr;
-    uint8_t* host = nullptr;
-    hipEvent_t ev{};
+    Parts d, h;  // the device buffer's arrays and the pinned host buffer's, same layout
+    // GPU entropy: device addresses of h.ent_head / h.qp / h.packed, where the pack kernel writes
+    int* hhead = nullptr;
+    int8_t* hqp = nullptr;
+    uint8_t* hout = nullptr;
+    Event ev;
     std::atomic<int> pending{0};
     std::atomic<int> host_coded{0};  // hybrid entropy: slices of a host-routed picture still open
     bool qp_dirty = true;  // the slot's device QP array may not hold the sequence QP
   };
-  // carve one slot buffer (device or host) into its arrays
-  struct Parts {
-    uint8_t *flags, *cu_log2, *intra, *ipm, *cbf, *dir, *tu;
-    int16_t *mv, *mv1;
-    unsigned long long* mask_y;
-    unsigned* mask_c;
-    int *count, *offset, *total;
-    int16_t* packed;
-    uint32_t* sao;
-    int8_t* qp;
-    int* ent_head;     // GPU entropy: status, seg_bytes[B], row_bytes[B][hc]
-  };
-  Parts carve(uint8_t* base) const {
-    const long B = cfg_.batch, U = g_.usz;
-    Parts p;
+  void carve_slot(Carve& c, Parts& p) const {
+    const size_t B = cfg_.batch, U = g_.usz, N = B * nctu_;
     // D2H order: flags (one byte per unit: the CU's cu_log2 / intra / cbf / dir, packed by
     // k_pack_flags) .. qp is the head every picture copies; ipm (I pictures) and mv1 (B
     // pictures) follow; the separate decision planes the kernels write stay on the device
     // and are re-expanded from the flags into the host slot by each segment's CABAC task.
-    uint8_t* q = base;
-    p.flags = q;
-    q += align(B * U);
-    p.mv = reinterpret_cast<int16_t*>(q);
-    q += align(B * U * 4);
-    p.mask_y = reinterpret_cast<unsigned long long*>(q);
-    q += align(B * nctu_ * 8);
-    p.mask_c = reinterpret_cast<unsigned*>(q);
-    q += align(B * nctu_ * 4);
-    p.offset = reinterpret_cast<int*>(q);
-    q += align(B * nctu_ * 4);
-    p.total = reinterpret_cast<int*>(q);
-    q += align(B * 4);
-    p.sao = reinterpret_cast<uint32_t*>(q);
-    q += align(B * nctu_ * 12);
-    p.qp = reinterpret_cast<int8_t*>(q);
-    q += align(B);
-    p.ipm = q;
-    q += align(B * U);
-    p.mv1 = reinterpret_cast<int16_t*>(q);
-    q += align(B * U * 4);
-    p.cu_log2 = q;
-    p.intra = q + B * U;
-    p.cbf = q + 2 * B * U;
-    p.dir = q + 3 * B * U;
-    p.tu = q + 4 * B * U;
-    q += align(B * U * 5);
-    p.packed = reinterpret_cast<int16_t*>(q);
-    q += align(B * cap_ * 2);
-    p.ent_head = reinterpret_cast<int*>(q);
-    q += gpu_ent_ ? align(ent_head_bytes(B, g_)) : 0;
-    p.count = nullptr;  // device count array lives in the scratch below
-    return p;
+    c.take(p.flags, B * U);
+    c.take(p.mv, B * U * 4);
+    c.take(p.mask_y, N * 8);
+    c.take(p.mask_c, N * 4);
+    c.take(p.offset, N * 4);
+    c.take(p.total, B * 4);
+    c.take(p.sao, N * 12);
+    c.take(p.qp, B);
+    c.take(p.ipm, B * U);
+    c.take(p.mv1, B * U * 4);
+    c.pack(p.cu_log2, B * U);  // the five decision planes: one region
+    c.pack(p.intra, B * U);
+    c.pack(p.cbf, B * U);
+    c.pack(p.dir, B * U);
+    c.take(p.tu, B * U);
+    c.take(p.packed, B * cap_ * 2);  // (the GPU entropy payload lands in the host slot's `packed`)
+    // head of the entropy outputs: status, seg_bytes[B], row_bytes[B][hc]
+    if (gpu_ent_) c.take(p.ent_head, 16 + 4 * B + 4 * B * g_.hc);
+  }
+  // Every buffer of the core, once: allocated from mem_, or only counted by a count-only mem_.
+  void layout() {
+    const size_t B = cfg_.batch, N = B * nctu_;
+    auto frame_set = [&](FrameSet& f) {
+      f.y = mem_.dev(B * g_.ysz);
+      f.u = mem_.dev(B * g_.csz);
+      f.v = mem_.dev(B * g_.csz);
+    };
+    frame_set(src_);
+    // Decoded picture buffer (tv/gop.h): every picture is reconstructed into a free DPB entry
+    // that keeps its final (deblocked + SAO) samples, the 16 quarter-pel phase planes of its
+    // luma (only when a later picture references it) and its quarter-res source luma (the
+    // coarse search's reference); an entry is free again once no later picture needs it.
+    // I P P P needs 2 entries, hierarchical-B mini-GOPs of M frames log2(M) + 2.  With SAO
+    // one scratch set holds the deblocked picture the filter reads.
+    for (int k = 0; k < ndpb_; ++k) {
+      frame_set(dpb_[k].rec);
+      dpb_[k].phase = mem_.dev(B * 16 * g_.psz);
+      dpb_[k].q = mem_.dev(B * (size_t)(g_.W / 4) * (g_.H / 4));
+    }
+    if (seq_.sao) frame_set(deb_);
+    coef_y_ = mem_.dev<int16_t>(B * g_.ysz * sizeof(int16_t));
+    coef_u_ = mem_.dev<int16_t>(B * g_.csz * sizeof(int16_t));
+    coef_v_ = mem_.dev<int16_t>(B * g_.csz * sizeof(int16_t));
+    d_sse_ = mem_.dev<unsigned long long>(B * 3 * sizeof(unsigned long long));
+    // per-CTB counts are consumed by the scan within the same frame: one scratch suffices
+    count_scratch_ = mem_.dev<int>(N * sizeof(int));
+    // hierarchical motion search: coarse field (+ cost) per list; B pictures: per-list fine
+    // search results for the bi decision
+    cmv_ = mem_.dev<int16_t>(2 * N * 2 * sizeof(int16_t));
+    ccost_ = mem_.dev<int>(2 * N * sizeof(int));
+    if (cfg_.mgop > 1) meout_ = mem_.dev<CtbMeOut>(2 * N * sizeof(CtbMeOut));
+    if (seq_.pintra) {  // intra-in-P scores and lists (tv/me_model.h pintra_*): 16 bytes per CTB each
+      Carve c;
+      c.take(pi_.qcost, N * 16);
+      c.take(pi_.gate, N * 16);
+      c.take(pi_.pass, N * 16);
+      c.take(pi_.clist, N * 16);
+      c.take(pi_.count, 6 * sizeof(int));
+      c.take(pi_.cand, N * 4);
+      c.bind(mem_.dev(c.size()));
+    }
+    if (gpu_ent_) {
+      // token capacity of a lane's scratch: one token per luma sample of every segment (the
+      // bench's textured I pictures use about a third of that; at QP 22 more than half); a
+      // picture that needs more is coded by the host writer instead (status != 0)
+      const char* per = getenv("TV_ENT_TOKENS_PER_PX");  // read per engine (tests shrink it)
+      tok_cap_ = (long)((per ? atof(per) : 1.0) * B * g_.ysz) + 1024;
+      ent_tab_ = mem_.dev<EntropyTables>(sizeof(EntropyTables));
+      // per-lane entropy scratch (each lane's stream codes one picture at a time): CTB token
+      // regions of the single binarisation pass, the picture's contiguous token lists (+ 64
+      // tokens of padding), coder output staging, CTB counts and offsets, segment totals and
+      // the rows' WPP hand-off
+      for (int l = 0; l < ent_lanes(); ++l) {
+        EntScratch& e = ent_[l];
+        Carve c;
+        c.take(e.regions, N * kEntRegionTokens * 4);
+        c.take(e.tokens, (tok_cap_ + 64) * 4);
+        c.take(e.stage, 3 * tok_cap_ + 20 * B * g_.hc + 16);
+        c.take(e.ctb_cnt, N * 4);
+        c.take(e.ctb_off, N * 4);
+        c.take(e.seg_tok, B * 4);
+        c.take(e.wflag, B * g_.hc * 4);
+        c.take(e.wctx, B * g_.hc * kEntCtx);
+        c.bind(mem_.dev(c.size()));
+        e.skip = mem_.dev(B * g_.usz);
+        e.midx = mem_.dev<int8_t>(B * g_.usz);
+      }
+      const char* dbg = getenv("TV_ENT_DEBUG");
+      if (dbg && *dbg == '1') ent_dbg_ = mem_.dev<unsigned long long>(8 * sizeof(unsigned long long));
+    }
+    qhost_ = mem_.host<int8_t>((size_t)cfg_.gop * B);
+    quni_ = mem_.host<int8_t>(B);
+    for (int k = 0; k < nslots_; ++k) {
+      Carve cd, ch;
+      carve_slot(cd, slots_[k].d);
+      carve_slot(ch, slots_[k].h);
+      cd.bind(mem_.dev(cd.size()));
+      ch.bind(mem_.host(ch.size()));
+    }
+    rc_ = mem_.dev<RcTables>(sizeof(RcTables));
   }
   DecisionSet slot_dec(const Slot& s) const {
-    const Parts p = carve(s.dev);
+    const Parts& p = s.d;
     DecisionSet d;
     d.qp = p.qp;
     d.cu_log2 = p.cu_log2;
@@ -589,29 +564,26 @@ class Core {
   // the slot's decisions of a B picture (direction and list-1 planes attached)
   DecisionSet slot_dec_b(const Slot& s) const {
     DecisionSet d = slot_dec(s);
-    const Parts p = carve(s.dev);
-    d.dir = p.dir;
-    d.mv1 = p.mv1;
+    d.dir = s.d.dir;
+    d.mv1 = s.d.mv1;
     return d;
   }
   CompactSet slot_compact(const Slot& s) const {
-    const Parts p = carve(s.dev);
+    const Parts& p = s.d;
     CompactSet c;
     c.mask_y = p.mask_y;
     c.mask_c = p.mask_c;
-    c.count = reinterpret_cast<int*>(coef_count_scratch());
+    c.count = count_scratch_;
     c.offset = p.offset;
     c.total = p.total;
     c.packed = p.packed;
     c.cap = cap_;
     return c;
   }
-  // per-CTB counts are consumed by the scan within the same frame: one scratch suffices
-  void* coef_count_scratch() const { return count_scratch_; }
 
   // segment b's decision planes in the host slot from the transferred flag bytes
   void expand_flags(const Slot& s, int b) const {
-    const Parts p = carve(s.host);
+    const Parts& p = s.h;
     const long U = g_.usz, o = b * U;
     for (long u = 0; u < U; ++u) {
       const uint8_t f = p.flags[o + u];
@@ -625,7 +597,7 @@ class Core {
   }
   // host view of segment b in a slot (compact levels)
   FrameData host_view(const Slot& s, int b, const SliceRefs* refs) const {
-    const Parts p = carve(s.host);
+    const Parts& p = s.h;
     const long U = g_.usz;
     FrameData f;
     f.w8 = g_.w8;
@@ -695,7 +667,7 @@ class Core {
   // picture (capacity), the caller falls back to the host writer
   bool fetch_entropy(Slot& s, int B) {
     wait_event(s.ev);  // the pack kernel wrote head, slice QPs and payload into the host slot
-    const Parts h = carve(s.host);
+    const Parts& h = s.h;
     if (h.ent_head[0] != 0) {
       ent_fallbacks_++;
       ent_status_ |= h.ent_head[0];
@@ -712,7 +684,7 @@ class Core {
   }
   // slice b of picture f from the GPU's substreams: header, entry points, emulation prevention
   void assemble_slice(const Slot& s, int b, int f) {
-    const Parts h = carve(s.host);
+    const Parts& h = s.h;
     const int* seg = h.ent_head + 4;
     const int* rows = h.ent_head + 4 + cfg_.batch + (long)b * g_.hc;
     long off = 0;
@@ -745,7 +717,7 @@ class Core {
     a.pic.max_merge = seq_.max_merge_cand;
     a.dec = dec;
     a.cs = slot_compact(s);
-    const Parts d = carve(s.dev);
+    const Parts& d = s.d;
     a.sao = seq_.sao ? d.sao : nullptr;
     a.skip = ent.skip;
     a.midx = ent.midx;
@@ -758,14 +730,13 @@ class Core {
     a.stage = ent.stage;
     a.wflag = ent.wflag;
     a.wctx = ent.wctx;
-    a.tab = ent.tab;
+    a.tab = ent_tab_;
     a.status = d.ent_head;
     a.seg_bytes = d.ent_head + 4;
     a.row_bytes = d.ent_head + 4 + cfg_.batch;
-    const Parts h = carve(s.host);  // the pack kernel's destination (pinned, device-visible)
-    HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.hhead), h.ent_head, 0));
-    HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.hqp), h.qp, 0));
-    HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.hout), h.packed, 0));
+    a.hhead = s.hhead;  // the pack kernel's destination: the host slot
+    a.hqp = s.hqp;
+    a.hout = s.hout;
     a.hout_cap = (long)cfg_.batch * cap_ * 2;
     a.dbg = ent_dbg_;
     return a;
@@ -774,10 +745,10 @@ class Core {
   void fetch_slot(Slot& s, int B, int ptype) {
     // the core's D2H stream: used by its one fetch thread only, destroyed with the core (a
     // thread_local stream outlived the engine and kept a hardware queue referenced)
-    if (!dstream_) HIP_OK(hipStreamCreateWithFlags(&dstream_, hipStreamNonBlocking));
+    if (!dstream_) HIP_OK(hipStreamCreateWithFlags(&dstream_.s, hipStreamNonBlocking));
     hipStream_t ws = dstream_;
     wait_event(s.ev);
-    const Parts d = carve(s.dev), h = carve(s.host);
+    const Parts &d = s.d, &h = s.h;
     const long U = g_.usz;
     // Every D2H copy is a blit-kernel launch (~10 us of CU time each): the full-batch case
     // moves the whole contiguous header (decision planes .. SAO params) in one copy and all
@@ -899,7 +870,7 @@ class Core {
     const FrameSet fin_set = cur_e.rec;
     const FrameSet cur = seq_.sao ? deb_ : fin_set;  // SAO filters deb_ into the entry
     DecisionSet dec = bpic ? slot_dec_b(s) : dec0;
-    if (!intra && seq_.rqt) dec.tu = carve(s.dev).tu;  // RQT: P and B pictures
+    if (!intra && seq_.rqt) dec.tu = s.d.tu;  // RQT: P and B pictures
     // TV_SYNC_DEBUG=1: synchronise and check after every stage (fault isolation)
     auto stage = [&](const char* name) {
       if (!sync_debug_) return;
@@ -940,11 +911,11 @@ class Core {
     }
     stage(intra ? "intra" : "inter");
     launch_compact(dec, g_, slot_compact(s), B, stream_);
-    launch_pack_flags(dec, carve(s.dev).flags, g_, B, stream_);
+    launch_pack_flags(dec, s.d.flags, g_, B, stream_);
     stage("compact");
     if (seq_.deblock) launch_deblock(cur, dec, g_, B, stream_);
     stage("deblock");
-    if (seq_.sao) launch_sao(src_, cur, fin_set, carve(s.dev).sao, dec.qp, rc_, g_, B, stream_, d_sse_);
+    if (seq_.sao) launch_sao(src_, cur, fin_set, s.d.sao, dec.qp, rc_, g_, B, stream_, d_sse_);
     stage("sao");
     cur_e.disp = pic.disp;
     if (pic.disp == F - 1) last_entry_ = e;
@@ -982,7 +953,7 @@ class Core {
         const char* e = getenv("TV_ENT_SERIAL");
         return e && *e == '1';
       }();
-      hipStream_t es = serial ? stream_ : estream_[lane];
+      hipStream_t es = serial ? stream_.s : estream_[lane].s;
       launch_entropy_bin(ea, B, es);
       launch_entropy_ac(ea, B, es);
       stage("entropy");
@@ -1053,18 +1024,9 @@ class Core {
     }
   }
 
-  // Single-core encode (groups == 1)
-  template <class Upload> void run(int nseg, int nframes, Upload&& upload) {
-    begin(nseg, nframes, nullptr);
-    for (int f = 0; f < nframes; ++f) issue(f, upload);
-    end_record();
-    finish();
-  }
-
   FrameSet src() const { return src_; }
   hipEvent_t t0() const { return t0_; }
   hipEvent_t t1() const { return t1_; }
-  long entropy_ns() const { return entropy_ns_; }
 
  private:
   // Slot hand-back: the host thread sleeps on a condition variable instead of spinning, so
@@ -1108,22 +1070,21 @@ class Core {
   }();
   int dense_after() const { return dense_after_; }
   int ent_lanes() const { return ent_lanes_; }
-  hipStream_t estream_[kMaxEntLanes] = {};
+  Stream estream_[kMaxEntLanes];
   std::atomic<int> ent_dense_run_{0};  // consecutive GPU-coded pictures above 0.01 bytes per sample
   long ent_lane_pics_[kMaxEntLanes] = {};
-  hipStream_t dstream_ = nullptr;  // D2H copies of host-coded slots (the fetch thread's)
-  hipEvent_t eev_ = nullptr;
+  Stream dstream_;  // D2H copies of host-coded slots (the fetch thread's)
+  Event eev_;
   struct EntScratch {
     uint8_t* skip = nullptr;
     int8_t* midx = nullptr;
-    uint8_t* base = nullptr;  // the ent_core_bytes() allocation
     uint32_t *regions = nullptr, *tokens = nullptr;
     uint8_t* stage = nullptr;
     int *ctb_cnt = nullptr, *ctb_off = nullptr, *seg_tok = nullptr, *wflag = nullptr;
     uint8_t* wctx = nullptr;
-    EntropyTables* tab = nullptr;
   } ent_[kMaxEntLanes];
-  long tok_cap_ = 0, slot_host_bytes_ = 0;
+  EntropyTables* ent_tab_ = nullptr;
+  long tok_cap_ = 0;
   unsigned long long* ent_dbg_ = nullptr;  // TV_ENT_DEBUG=1: coder counters (EntropyArgs::dbg)
   std::atomic<long> ent_fallbacks_{0};
   std::atomic<long> ent_host_pics_{0};
@@ -1137,8 +1098,9 @@ class Core {
   bool qmap_given_ = false;  // an explicit QP map (2-pass plan) overrides in-engine CRF
   int8_t* qhost_ = nullptr;  // pinned [frame][segment] slice QPs of the current call
   int8_t* quni_ = nullptr;   // pinned: the sequence QP for every segment slot
-  hipStream_t stream_{}, istream_{};
-  hipEvent_t iev_[2]{};
+  Stream stream_, istream_;
+  Event iev_[2], t0_, t1_;
+  Arena mem_;  // after the streams and events: freed before they are destroyed
   static constexpr int kMaxDpb = 8;
   struct DpbEntry {
     FrameSet rec{};
@@ -1155,10 +1117,9 @@ class Core {
   PIntraBuffers pi_{};  // qcost == nullptr: intra-in-P off (TV_PINTRA=0)
   int16_t *coef_y_ = nullptr, *coef_u_ = nullptr, *coef_v_ = nullptr;
   unsigned long long* d_sse_ = nullptr;
-  void* count_scratch_ = nullptr;
+  int* count_scratch_ = nullptr;
   int16_t* cmv_ = nullptr;
   int* ccost_ = nullptr;
-  long qsz_ = 0;
   int nctu_ = 0;
   int last_frames_ = 1;
   const bool sync_debug_ = [] {
@@ -1168,8 +1129,6 @@ class Core {
   long cap_ = 0;
   std::unique_ptr<Slot[]> slots_;
   int nslots_ = 0;
-  long slot_bytes_ = 0;
-  hipEvent_t t0_{}, t1_{};
   ThreadPool* pool_;
   int B_ = 0, F_ = 0;
   std::vector<std::vector<std::vector<uint8_t>>> slices_;
@@ -1191,19 +1150,24 @@ class Core {
 // motion search / reconstruction kernels fill the rest of the GPU.
 class Engine {
  public:
-  explicit Engine(const EngineCfg& c) : cfg_(c) {
+  // each core's configuration: the batch split into at most `groups` cores of ceil(batch /
+  // groups) segments (the last one takes what is left)
+  static std::vector<EngineCfg> split(const EngineCfg& c) {
     if (c.batch < 1 || c.batch > kMaxBatch) throw std::runtime_error("batch must be 1..64");
-    HIP_OK(hipSetDevice(c.device));
-    int G = c.groups < 1 ? 1 : c.groups;
-    if (G > c.batch) G = c.batch;
-    per_ = (c.batch + G - 1) / G;
-    G = (c.batch + per_ - 1) / per_;
-    pool_ = std::make_unique<ThreadPool>(c.threads, c.device);
-    for (int g = 0; g < G; ++g) {
-      EngineCfg cc = c;
-      cc.batch = std::min(per_, c.batch - g * per_);
-      cores_.push_back(std::make_unique<Core>(cc, pool_.get()));
+    const int G = std::min(std::max(c.groups, 1), c.batch), per = (c.batch + G - 1) / G;
+    std::vector<EngineCfg> v;
+    for (int left = c.batch; left > 0; left -= per) {
+      v.push_back(c);
+      v.back().batch = std::min(per, left);
     }
+    return v;
+  }
+  explicit Engine(const EngineCfg& c) : cfg_(c) {
+    const std::vector<EngineCfg> parts = split(c);
+    per_ = parts[0].batch;
+    HIP_OK(hipSetDevice(c.device));
+    pool_ = std::make_unique<ThreadPool>(c.threads, c.device);
+    for (const EngineCfg& cc : parts) cores_.push_back(std::make_unique<Core>(cc, pool_.get()));
     for (int l = 0; l < 4; ++l)  // Core::kMaxEntLanes
       for (auto& core : cores_) core->init_entropy_stream(l);
   }
@@ -1310,14 +1274,8 @@ class Engine {
   }
   // footprint of an engine of config c (the group split of the constructor), no allocation
   static void estimate(const EngineCfg& c, size_t& dev, size_t& host) {
-    int G = c.groups < 1 ? 1 : c.groups;
-    if (G > c.batch) G = c.batch;
-    const int per = (c.batch + G - 1) / G;
-    G = (c.batch + per - 1) / per;
     dev = host = 0;
-    for (int g = 0; g < G; ++g) {
-      EngineCfg cc = c;
-      cc.batch = std::min(per, c.batch - g * per);
+    for (const EngineCfg& cc : split(c)) {
       size_t d = 0, h = 0;
       Core::estimate(cc, d, h);
       dev += d;
@@ -1387,6 +1345,16 @@ template <class F> int gguard(F&& f) {
     return -1;
   }
 }
+tv::gpu::EngineCfg engine_cfg(int width, int height, int qp, int batch, int gop, int range, int flags, uint32_t seed,
+                              int threads, int device, int max_merge, int crf, int mgop) {
+  // TV_ENGINE_GROUPS: segment groups on separate streams, one frame apart (default 2)
+  const char* ge = getenv("TV_ENGINE_GROUPS");
+  const int groups = ge ? std::max(1, atoi(ge)) : (batch >= 2 ? 2 : 1);
+  if (crf < 0 || crf > 51) throw std::runtime_error("crf must be 0 (off) or 1..51");
+  tv::gpu::EngineCfg c{width, height, qp, batch, gop, range, flags, threads, device, max_merge, seed, groups, crf};
+  c.mgop = mgop;
+  return c;
+}
 }  // namespace
 
 extern "C" {
@@ -1398,30 +1366,14 @@ int tv_gpu_device_count() {
   return n;
 }
 
-void* tv_engine_new(int width, int height, int qp, int batch, int gop, int range, int deblock,
-                    uint32_t seed, int threads, int device, int max_merge, int crf) {
-  void* r = nullptr;
-  gguard([&] {
-    // TV_ENGINE_GROUPS: segment groups on separate streams, one frame apart (default 2)
-    const char* ge = getenv("TV_ENGINE_GROUPS");
-    const int groups = ge ? std::max(1, atoi(ge)) : (batch >= 2 ? 2 : 1);
-    if (crf < 0 || crf > 51) throw std::runtime_error("crf must be 0 (off) or 1..51");
-    tv::gpu::EngineCfg c{width, height, qp, batch, gop, range, deblock, threads, device, max_merge, seed, groups, crf};
-    r = new tv::gpu::Engine(c);
-  });
-  return r;
-}
-// hierarchical-B engine (tv/gop.h): mgop = mini-GOP size (power of 2; 1 = I P P P)
+// mgop = mini-GOP size of the hierarchical-B structure (tv/gop.h; power of 2; 1 = I P P P);
+// `deblock`: the configuration bits (tv::kFlag*)
 void* tv_engine_new_b(int width, int height, int qp, int batch, int gop, int range, int deblock, uint32_t seed,
                       int threads, int device, int max_merge, int crf, int mgop) {
   void* r = nullptr;
   gguard([&] {
-    const char* ge = getenv("TV_ENGINE_GROUPS");
-    const int groups = ge ? std::max(1, atoi(ge)) : (batch >= 2 ? 2 : 1);
-    if (crf < 0 || crf > 51) throw std::runtime_error("crf must be 0 (off) or 1..51");
-    tv::gpu::EngineCfg c{width, height, qp, batch, gop, range, deblock, threads, device, max_merge, seed, groups, crf};
-    c.mgop = mgop;
-    r = new tv::gpu::Engine(c);
+    r = new tv::gpu::Engine(engine_cfg(width, height, qp, batch, gop, range, deblock, seed, threads, device,
+                                       max_merge, crf, mgop));
   });
   return r;
 }
@@ -1465,12 +1417,8 @@ long long tv_engine_entropy_lane_pictures(void* e, int lane) {
 int tv_engine_estimate(int width, int height, int batch, int gop, int deblock, int mgop, unsigned long long* dev,
                        unsigned long long* host) {
   return gguard([&] {
-    const char* ge = getenv("TV_ENGINE_GROUPS");
-    const int groups = ge ? std::max(1, atoi(ge)) : (batch >= 2 ? 2 : 1);
-    tv::gpu::EngineCfg c{width, height, 27, batch, gop, 64, deblock, 1, 0, 5, 1u, groups, 0};
-    c.mgop = mgop;
     size_t d = 0, h = 0;
-    tv::gpu::Engine::estimate(c, d, h);
+    tv::gpu::Engine::estimate(engine_cfg(width, height, 27, batch, gop, 64, deblock, 1u, 1, 0, 5, 0, mgop), d, h);
     *dev = d;
     *host = h;
   });

@@ -25,6 +25,19 @@
 
 namespace tv {
 
+// Configuration bits of the C APIs' `deblock` argument (SeqConfig::set_flags; the same names
+// and values in thinvids_amd/models/hevc.py, checked by tests/test_codec_tools.py)
+constexpr int kFlagDeblock = 1;
+constexpr int kFlagSao = 2;
+constexpr int kFlagWpp = 4;           // one CABAC substream per CTB row
+constexpr int kFlagNoRqt = 8;
+constexpr int kFlagNoPIntra = 16;     // no intra CUs in P pictures
+constexpr int kFlagHostEntropy = 32;  // GPU engine only: CABAC by the host writer, not k_entropy.hip
+constexpr int kFlagCascade = 64;      // I P P P QP cascade
+constexpr int kFlagNoRdoq = 128;
+constexpr int kFlagSubpelSatd = 256;
+constexpr int kFlagSignHiding = 512;
+
 struct SeqConfig {
   int width = 0, height = 0;      // display size (conformance window)
   int coded_w = 0, coded_h = 0;   // multiples of the CTB size
@@ -59,19 +72,17 @@ struct SeqConfig {
   // All of these change the bitstream: they are explicit configuration (the C API's flag bits 3 / 4,
   // EncodeSpec.rqt / .pintra, part of the engine key and the checkpoint fingerprint), never
   // read from the environment here.
-  // Flag bits of the C API's `deblock` argument: 1 deblocking, 2 SAO, 4 WPP, 8 no RQT,
-  // 16 no intra-in-P (32: GPU engine only, CABAC on the host), 64 I P P P QP cascade,
-  // 128 no RDOQ-lite, 256 SATD sub-pel decision, 512 sign data hiding
+  // `f`: the kFlag* bits above (the C API's `deblock` argument)
   void set_flags(int f) {
-    sign_hiding = (f & 512) != 0;
-    subpel_satd = (f & 256) != 0;
-    deblock = (f & 1) != 0;
-    sao = (f & 2) != 0;
-    wpp = (f & 4) != 0;
-    rqt = !(f & 8);
-    pintra = !(f & 16);
-    cascade = (f & 64) != 0;
-    rdoq = !(f & 128);
+    deblock = (f & kFlagDeblock) != 0;
+    sao = (f & kFlagSao) != 0;
+    wpp = (f & kFlagWpp) != 0;
+    rqt = !(f & kFlagNoRqt);
+    pintra = !(f & kFlagNoPIntra);
+    cascade = (f & kFlagCascade) != 0;
+    rdoq = !(f & kFlagNoRdoq);
+    subpel_satd = (f & kFlagSubpelSatd) != 0;
+    sign_hiding = (f & kFlagSignHiding) != 0;
   }
   int fps_num = 30, fps_den = 1;
   void finalize() {

@@ -28,6 +28,20 @@ def test_codec_flags_bits():
     assert hevc.codec_flags(rdoq=False) == 1 | 4 | 128
 
 
+def test_flag_names_match_the_native_header():
+    """The FLAG_* names of models/hevc.py are the kFlag* constants of tv/hevc_codec.h, bit for bit."""
+    import re
+    from pathlib import Path
+
+    text = (Path(__file__).resolve().parent.parent / "csrc" / "include" / "tv" / "hevc_codec.h").read_text()
+    native = {name: int(v) for name, v in re.findall(r"constexpr int kFlag(\w+) = (\d+);", text)}
+    want = {"Deblock": 1, "Sao": 2, "Wpp": 4, "NoRqt": 8, "NoPIntra": 16, "HostEntropy": 32, "Cascade": 64,
+            "NoRdoq": 128, "SubpelSatd": 256, "SignHiding": 512}
+    assert native == want
+    py = {k[5:].replace("_", "").lower(): v for k, v in vars(hevc).items() if k.startswith("FLAG_")}
+    assert py == {k.lower(): v for k, v in native.items()}
+
+
 def test_tools_change_the_stream_and_env_does_not(monkeypatch):
     fr = _frames()
     kw = dict(qp=27, search_range=16, sao=True)

@@ -66,17 +66,57 @@ def test_auto_batch_is_capped_by_the_budget():
     assert auto_batch(EncodeSpec(3840, 2160, codec="av1"), 1000 * GiB) == 16
 
 
+# geometries that reach every optional buffer: the minimum size (two CTB columns, the least the
+# GPU coder accepts), an uneven 2 + 1 group split, no intra-in-P block, no WPP, a deep DPB with
+# the SAO scratch set; each with the GPU coder's scratch and without it
+_EDGES = [(64, 64, 1, 2, False, 1, {}), (96, 64, 3, 4, False, 1, {}), (320, 180, 8, 16, False, 1, {"pintra": False}),
+          (320, 180, 8, 16, False, 1, {"wpp": False}), (320, 180, 8, 16, True, 8, {})]
+
+
+def _row(w, h, batch, gop, sao, bframes, kw={}, lanes=None):
+    extra = [f"{k}={v}" for k, v in kw.items()] + ([f"lanes={lanes}"] if lanes else [])
+    return pytest.param(w, h, batch, gop, sao, bframes, kw, lanes,
+                        id="-".join(str(x) for x in (w, h, batch, gop, sao, bframes, *extra)))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("w,h,batch,gop,sao,bframes", [(1920, 1080, 48, 64, True, 1), (320, 180, 8, 16, False, 8),
-                                                       (3840, 2160, 6, 8, True, 1)])
-def test_native_footprint_equals_estimate(w, h, batch, gop, sao, bframes):
+@pytest.mark.parametrize("w,h,batch,gop,sao,bframes,kw,lanes",
+                         [_row(1920, 1080, 48, 64, True, 1), _row(320, 180, 8, 16, False, 8),
+                          _row(3840, 2160, 6, 8, True, 1)]
+                         + [_row(*e[:6], dict(e[6], entropy=ent)) for e in _EDGES for ent in ("gpu", "host")]
+                         + [_row(320, 180, 8, 16, True, 1, {"entropy": "gpu"}, "4")])
+def test_native_footprint_equals_estimate(w, h, batch, gop, sao, bframes, kw, lanes, monkeypatch):
     from thinvids_amd.models.gpu_engine import GpuEngine, estimate_footprint
 
-    eng = GpuEngine(width=w, height=h, qp=27, batch=batch, gop=gop, sao=sao, bframes=bframes)
+    if lanes:
+        monkeypatch.setenv("TV_ENT_LANES", lanes)
+    eng = GpuEngine(width=w, height=h, qp=27, batch=batch, gop=gop, sao=sao, bframes=bframes, **kw)
     try:
-        assert eng.footprint() == estimate_footprint(w, h, batch, gop, sao, bframes)
+        assert eng.footprint() == estimate_footprint(w, h, batch, gop, sao, bframes, **kw)
+        if "entropy" in kw:
+            assert eng.entropy_stats()["gpu"] == (kw["entropy"] == "gpu" and kw.get("wpp", True))
     finally:
         eng.close()
+
+
+@pytest.mark.gpu
+def test_refused_configuration_leaves_the_device_usable():
+    """A configuration the constructor refuses is refused before anything is allocated, and an
+    engine built right afterwards codes what the golden encoder codes."""
+    from thinvids_amd.models import hevc
+    from thinvids_amd.models.gpu_engine import GpuEngine
+
+    with pytest.raises(RuntimeError, match="power of 2"):
+        GpuEngine(64, 64, batch=1, gop=2, bframes=3)
+    with pytest.raises(RuntimeError, match="CRF"):
+        GpuEngine(64, 64, batch=1, gop=2, bframes=8, crf=23)
+    eng = GpuEngine(64, 64, batch=1, gop=2)
+    try:
+        seg, = eng.encode_synthetic([0])
+    finally:
+        eng.close()
+    frames = [hevc.synth_frame(1, f, 64, 64) for f in range(2)]  # the engine's default seed
+    assert seg == hevc.encode_sequence_cpu(frames)[0]
 
 
 @pytest.mark.gpu

@@ -124,7 +124,6 @@ GPU = {
     "tv_gpu_build_hash": (cstr, []),
     "tv_gpu_last_error": (cstr, []),
     "tv_gpu_device_count": (i, []),
-    "tv_engine_new": (vp, [i] * 7 + [u32, i, i, i, i]),
     "tv_engine_new_b": (vp, [i] * 7 + [u32, i, i, i, i, i]),
     "tv_engine_free": (None, [vp]),
     "tv_engine_encode_synth": (i, [vp, i32p, i, i, vp]),

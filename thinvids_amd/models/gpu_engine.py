@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from .._native import gpu_lib, ok, ptr
-from .hevc import coded_size
+from .hevc import FLAG_HOST_ENTROPY, codec_flags, coded_size
 
 
 def device_count() -> int:
@@ -78,11 +78,9 @@ class GpuEngine:
         self.sao = sao
         self.device = device
         self.bframes = int(bframes)
-        from .hevc import codec_flags
-
         self.entropy = resolve_entropy(entropy) if wpp else "host"
         self.flags = (codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding)
-                      | (32 if self.entropy == "host" else 0))
+                      | (FLAG_HOST_ENTROPY if self.entropy == "host" else 0))
         self.h = self.lib.tv_engine_new_b(width, height, qp, batch, gop, search_range, self.flags,
                                           seed & 0xFFFFFFFF, self.threads, device, max_merge, int(crf), self.bframes)
         if not self.h:
@@ -241,11 +239,10 @@ def estimate_footprint(width: int, height: int, batch: int, gop: int, sao: bool 
                        sign_hiding: bool = False) -> dict:
     """HBM / pinned-host bytes an engine of this geometry would allocate, computed by the
     native constructor's own size formulas without allocating (tv_engine_estimate)."""
-    from .hevc import codec_flags
-
     lib = gpu_lib()
     ent = resolve_entropy(entropy) if wpp else "host"
-    flags = codec_flags(True, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding) | (32 if ent == "host" else 0)
+    flags = codec_flags(True, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding)
+    flags |= FLAG_HOST_ENTROPY if ent == "host" else 0
     d, h = C.c_ulonglong(), C.c_ulonglong()
     ok(lib.tv_engine_estimate(width, height, batch, gop, flags, int(bframes), C.byref(d), C.byref(h)),
        lib, "tv_gpu_last_error", ValueError)

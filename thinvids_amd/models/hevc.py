@@ -39,15 +39,27 @@ def psnr_yuv(ref: Frame, dec: Frame) -> dict:
     return {"y": py, "u": pu, "v": pv, "yuv": (6 * py + pu + pv) / 8}
 
 
+# The native APIs' configuration bits: the kFlag* constants of csrc/include/tv/hevc_codec.h
+# (tests/test_codec_tools.py compares the two lists)
+FLAG_DEBLOCK = 1
+FLAG_SAO = 2
+FLAG_WPP = 4  # WPP substreams
+FLAG_NO_RQT = 8  # no residual quadtree
+FLAG_NO_PINTRA = 16  # no intra CUs in P pictures
+FLAG_HOST_ENTROPY = 32  # GPU engine only: CABAC by the host writer
+FLAG_CASCADE = 64  # the constant-QP I P P P QP cascade (tv/gop.h ippp_qp_offset)
+FLAG_NO_RDOQ = 128  # no RDOQ-lite coefficient-group trimming (tv/hevc_defs.h kRdoqMode)
+FLAG_SUBPEL_SATD = 256  # half- / quarter-pel vectors chosen by SATD + MV rate (tv/me_model.h)
+FLAG_SIGN_HIDING = 512  # sign data hiding (tv/sdh.h)
+
+
 def codec_flags(deblock: bool = True, sao: bool = False, wpp: bool = True, rqt: bool = True, pintra: bool = True,
                 cascade: bool = False, rdoq: bool = True, subpel_satd: bool = False, sign_hiding: bool = False) -> int:
-    """The native APIs' configuration bits (tv::SeqConfig::set_flags): 1 deblocking, 2 SAO,
-    4 WPP substreams, 8 no residual quadtree, 16 no intra CUs in P pictures, 64 the constant-QP
-    I P P P QP cascade (tv/gop.h ippp_qp_offset), 128 no RDOQ-lite coefficient-group trimming
-    (tv/hevc_defs.h kRdoqMode), 256 half- / quarter-pel vectors chosen by SATD + MV rate
-    (tv/me_model.h; off by default), 512 sign data hiding (tv/sdh.h; off by default)."""
-    return (int(bool(deblock)) | (2 if sao else 0) | (4 if wpp else 0) | (0 if rqt else 8) | (0 if pintra else 16)
-            | (64 if cascade else 0) | (0 if rdoq else 128) | (256 if subpel_satd else 0) | (512 if sign_hiding else 0))
+    """The native APIs' configuration word (tv::SeqConfig::set_flags) from the tools' switches;
+    SATD sub-pel and sign data hiding are off by default."""
+    on = {FLAG_DEBLOCK: deblock, FLAG_SAO: sao, FLAG_WPP: wpp, FLAG_NO_RQT: not rqt, FLAG_NO_PINTRA: not pintra,
+          FLAG_CASCADE: cascade, FLAG_NO_RDOQ: not rdoq, FLAG_SUBPEL_SATD: subpel_satd, FLAG_SIGN_HIDING: sign_hiding}
+    return sum(bit for bit, v in on.items() if v)
 
 
 IPPP_CASCADE_IDR = -5
@@ -248,7 +260,7 @@ def write_frame(width: int, height: int, qp: int, idr: bool, poc: int, dec: dict
     lib = core_lib()
     out = Bytes()
     cy, cu, cv = (np.ascontiguousarray(c, dtype=np.int16) for c in coef)
-    check(lib.tv_write_frame(width, height, qp, int(bool(deblock)) | (512 if sign_hiding else 0), max_merge, int(idr), poc,
+    check(lib.tv_write_frame(width, height, qp, codec_flags(deblock, wpp=False, sign_hiding=sign_hiding), max_merge, int(idr), poc,
                              ptr(np.ascontiguousarray(dec["cu_log2"])), ptr(np.ascontiguousarray(dec["intra"])),
                              ptr(np.ascontiguousarray(dec["ipm"])),
                              ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16)),
@@ -273,7 +285,7 @@ def reconstruct_reference(width: int, height: int, qp: int, src: Frame, ref: Fra
     r = [np.ascontiguousarray(p) for p in ref] if ref is not None else None
     null = C.cast(None, C.POINTER(C.c_uint8))
     check(lib.tv_reconstruct_frame(
-        width, height, qp, int(bool(deblock)) | (512 if sign_hiding else 0), ptr(s[0]), ptr(s[1]), ptr(s[2]),
+        width, height, qp, codec_flags(deblock, wpp=False, sign_hiding=sign_hiding), ptr(s[0]), ptr(s[1]), ptr(s[2]),
         ptr(r[0]) if r else null, ptr(r[1]) if r else null, ptr(r[2]) if r else null,
         ptr(np.ascontiguousarray(dec["cu_log2"])), ptr(np.ascontiguousarray(dec["intra"])),
         ptr(np.ascontiguousarray(dec["ipm"])), ptr(np.ascontiguousarray(dec["mv"], dtype=np.int16)),
