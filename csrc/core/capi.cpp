@@ -12,6 +12,7 @@
 #include "tv/me_model.h"
 #include "tv/sdh.h"
 #include "tv/synth.h"
+#include "tv/synth_tile.h"
 #include "tv/tb_frag.h"
 
 using namespace tv;
@@ -30,6 +31,82 @@ template <class F> int guard(F&& f) {
 struct Bytes {
   std::vector<uint8_t> v;
 };
+
+// Host image of one octave's tables over a tile (tv/synth_tile.h): what the generator kernel
+// keeps in LDS.  px / py: the octave's 1/16-pel coordinate of every column / row of the tile.
+struct TileOctave {
+  int nx = 0;
+  std::vector<uint8_t> lat;
+  std::vector<uint16_t> top;
+  std::vector<int> cy, sy;
+  void build(int lp, uint32_t seed, const std::vector<int32_t>& px, const std::vector<int32_t>& py) {
+    const SynthWin w = synth_win(lp, seed, px.front(), px.back(), py.front(), py.back());
+    nx = (int)px.size();
+    lat.resize((size_t)w.npx * w.npy);
+    for (int r = 0; r < w.npy; ++r)
+      for (int i = 0; i < w.npx; ++i) lat[(size_t)r * w.npx + i] = (uint8_t)synth_win_lattice(w, i, r);
+    top.resize((size_t)w.npy * nx);
+    for (int x = 0; x < nx; ++x) {
+      int ci, sx;
+      synth_axis(px[x], w.sh, w.cx0, ci, sx);
+      for (int r = 0; r < w.npy; ++r)
+        top[(size_t)r * nx + x] = (uint16_t)synth_top(lat[(size_t)r * w.npx + ci], lat[(size_t)r * w.npx + ci + 1], sx);
+    }
+    cy.resize(py.size());
+    sy.resize(py.size());
+    for (size_t y = 0; y < py.size(); ++y) synth_axis(py[y], w.sh, w.cy0, cy[y], sy[y]);
+  }
+  int at(int x, int y) const {
+    const uint16_t* t = &top[(size_t)cy[y] * nx + x];
+    return synth_rows(t[0], t[nx], sy[y]);
+  }
+};
+
+// One tile of plane c of the coded picture (pitch pw), as the kernel's workgroup does it.
+void synth_tile_fill(const SynthFrameCtx& f, int c, int x0, int y0, int nx, int ny, int pw, uint8_t* P) {
+  const int s = c ? 1 : 0, dw = c ? f.W / 2 : f.W, dh = c ? f.H / 2 : f.H;
+  const bool tex = synth_textured(f.seed);
+  std::vector<int32_t> px(nx), py(ny), qx(nx), qy(ny);
+  for (int x = 0; x < nx; ++x) px[x] = synth_tile_pos(x0 + x, dw, s);
+  for (int y = 0; y < ny; ++y) py[y] = synth_tile_pos(y0 + y, dh, s);
+  std::vector<int> v((size_t)nx * ny);
+  TileOctave oct[4];
+  for (int x = 0; x < nx; ++x) qx[x] = px[x] + f.t * synth_pan_x(tex);
+  for (int y = 0; y < ny; ++y) qy[y] = py[y] + f.t * synth_pan_y(tex);
+  const int nb = synth_bg_octaves(c, tex);
+  for (int i = 0; i < nb; ++i) oct[i].build(synth_bg_lp(c, i), synth_bg_seed(f.seed, c, i), qx, qy);
+  for (int y = 0; y < ny; ++y)
+    for (int x = 0; x < nx; ++x) {
+      int n[4] = {0, 0, 0, 0};
+      for (int i = 0; i < nb; ++i) n[i] = oct[i].at(x, y);
+      v[(size_t)y * nx + x] = synth_bg_mix(c, tex, n);
+    }
+  for (int k = 0; k < kSynthObjects; ++k) {  // ascending: later objects on top
+    const SynthObject& o = f.obj[k];
+    int32_t xlo, xhi, ylo, yhi;
+    synth_obj_range(px.front(), px.back(), f.ox[k], o.w, xlo, xhi);
+    synth_obj_range(py.front(), py.back(), f.oy[k], o.h, ylo, yhi);
+    if (xlo > xhi || ylo > yhi) continue;  // the tile misses the bounding box
+    for (int x = 0; x < nx; ++x) qx[x] = clip3(xlo, xhi, px[x] - f.ox[k]);
+    for (int y = 0; y < ny; ++y) qy[y] = clip3(ylo, yhi, py[y] - f.oy[k]);
+    const int no = synth_obj_octaves(c), base = synth_obj_base(f.seed, k, c);
+    for (int i = 0; i < no; ++i) oct[i].build(synth_obj_lp(c, i), synth_obj_seed(o, c, i), qx, qy);
+    for (int y = 0; y < ny; ++y)
+      for (int x = 0; x < nx; ++x) {
+        const int32_t rx16 = px[x] - f.ox[k], ry16 = py[y] - f.oy[k];
+        if (rx16 != qx[x] || ry16 != qy[y] || synth_cover_col(o, rx16) > synth_cover_row(o, ry16)) continue;
+        int n[2] = {0, 0};
+        for (int i = 0; i < no; ++i) n[i] = oct[i].at(x, y);
+        v[(size_t)y * nx + x] = synth_obj_mix(c, base, n);
+      }
+  }
+  for (int y = 0; y < ny; ++y)
+    for (int x = 0; x < nx; ++x) {
+      int r = v[(size_t)y * nx + x];
+      if (tex) r += synth_grain(f.seed, f.t, c, tv_min(x0 + x, dw - 1), tv_min(y0 + y, dh - 1));
+      P[(size_t)(y0 + y) * pw + x0 + x] = (uint8_t)clip_pixel(r);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -53,6 +130,22 @@ void tv_synth_frame(uint32_t seed, int t, int W, int H, uint8_t* y, uint8_t* u, 
     const int w = c ? W / 2 : W, h = c ? H / 2 : H;
     for (int j = 0; j < h; ++j)
       for (int i = 0; i < w; ++i) P[(size_t)j * w + i] = (uint8_t)synth_sample_ctx(ctx, c, i, j);
+  }
+}
+
+// The frame at the coded size (width and height rounded up to kCtb, edge replicated), built
+// tile by tile with the tables of tv/synth_tile.h: the host mirror of the generator kernel.
+void tv_synth_frame_tiled(uint32_t seed, int t, int W, int H, int tile_w, int tile_h, uint8_t* y, uint8_t* u,
+                          uint8_t* v) {
+  SynthFrameCtx ctx;
+  synth_frame_ctx(seed, t, W, H, ctx);
+  const int cw = (W + kCtb - 1) / kCtb * kCtb, ch = (H + kCtb - 1) / kCtb * kCtb;
+  for (int c = 0; c < 3; ++c) {
+    uint8_t* P = c == 0 ? y : (c == 1 ? u : v);
+    const int pw = c ? cw / 2 : cw, ph = c ? ch / 2 : ch;
+    for (int y0 = 0; y0 < ph; y0 += tile_h)
+      for (int x0 = 0; x0 < pw; x0 += tile_w)
+        synth_tile_fill(ctx, c, x0, y0, tv_min(tile_w, pw - x0), tv_min(tile_h, ph - y0), pw, P);
   }
 }
 

@@ -5,129 +5,220 @@
 #include "gpu_common.h"
 #include "k_encode.h"
 #include "tv/synth.h"
+#include "tv/synth_tile.h"
 
 namespace tv {
 namespace gpu {
 
 // ---------------------------------- synthetic source ------------------------------------
-// One workgroup row-tile; the per-frame object trajectories are evaluated once per
-// workgroup into LDS (they were 18 hashes per pixel before).  Each thread produces 4
-// horizontally adjacent samples (one dword store): the value-noise octaves keep their
-// lattice-corner hashes across the 4 samples (a cell is >= 4 px wide, so the cell changes at
-// most once: 2 new hashes instead of 4 per octave per sample), and the row terms (cell row,
-// vertical smoothstep) are computed once.  Bit-identical to synth_sample_ctx (tv/synth.h),
-// which the CPU golden encoder uses.
-struct VNoiseRow {
-  int sh, sy;
-  int32_t cy, cx;
-  uint32_t seed;
-  int a, b, c, d;
-  __device__ void init(int32_t py16, int lp, uint32_t sd) {
-    sh = lp + 4;
-    seed = sd;
-    cy = py16 >> sh;
-    const int fy = (int)((py16 - (cy << sh)) << 8 >> sh);
-    sy = (fy * fy * (768 - 2 * fy)) >> 16;
-    cx = INT32_MIN;
-  }
-  __device__ int eval(int32_t px16) {
-    const int32_t nx = px16 >> sh;
-    if (nx != cx) {
-      if (nx == cx + 1) {
-        a = b;
-        c = d;
-      } else {
-        a = synth_hash(nx, cy, seed) & 255;
-        c = synth_hash(nx, cy + 1, seed) & 255;
-      }
-      b = synth_hash(nx + 1, cy, seed) & 255;
-      d = synth_hash(nx + 1, cy + 1, seed) & 255;
-      cx = nx;
-    }
-    const int fx = (int)((px16 - (cx << sh)) << 8 >> sh);
-    const int sx = (fx * fx * (768 - 2 * fx)) >> 16;
-    const int top = a * 256 + (b - a) * sx;
-    const int bot = c * 256 + (d - c) * sx;
-    return (top * 256 + (bot - top) * sy) >> 16;
-  }
-};
+// One workgroup per 256 x 32 tile of one plane of one segment, in the separable form of
+// tv/synth_tile.h (bit-identical to synth_sample_ctx of tv/synth.h, which the CPU golden
+// encoder uses; tests/test_synth_tiles.py walks the same routines on the host):
+//   1. the lattice hashes of every octave's window over the tile go into LDS, one point per
+//      lane, a lattice row per wave;
+//   2. thread x builds column x of every octave's `top` rows (16-bit) from them: the cell
+//      index and the horizontal smoothstep are taken once per column and octave;
+//   3. a lane takes 4 adjacent samples of 8 rows: per row and octave two 8-byte LDS reads and
+//      the vertical blend, whose cell row and smoothstep are wave-uniform.  A wave writes
+//      256 contiguous bytes of a row with one dword store per lane.
+// An object whose bounding box meets the tile (workgroup-uniform; most tiles meet none) has
+// its two octaves' tables built the same way in object-relative coordinates, reusing the LDS,
+// and is applied in ascending k so later objects stay on top; the ellipse test is a 64-bit
+// compare of a per-column with a per-row term (synth_cover_col / _row).  The frame contexts (object
+// trajectories) are computed by the launcher and travel as kernel arguments: no workgroup
+// evaluates synth_frame_ctx.
+constexpr int kSynTW = kSynthTileW, kSynTH = kSynthTileH, kSynRows = kSynTH / 4;  // rows per wave
+static_assert(kSynTW == 256 && kSynTH % 4 == 0, "a wave of 4-sample items spans the tile; 4 waves share its rows");
 
-__device__ __forceinline__ int synth_objects(const SynthFrameCtx& f, int c, int xl, int yl, int v, unsigned rows) {
-  for (; rows; rows &= rows - 1) {  // later objects on top: ascending k over the row's objects
-    const int k = __builtin_ctz(rows);
-    const SynthObject& o = f.obj[k];
-    const int32_t rx16 = xl * 16 - f.ox[k], ry16 = yl * 16 - f.oy[k];
-    if (rx16 < 0 || rx16 >= o.w * 16) continue;
-    if (o.shape == 1) {
-      const int64_t dx = 2 * (int64_t)rx16 - o.w * 16, dy = 2 * (int64_t)ry16 - o.h * 16;
-      const int64_t ww = (int64_t)o.w * 16, hh = (int64_t)o.h * 16;
-      if (dx * dx * hh * hh + dy * dy * ww * ww > ww * ww * hh * hh) continue;
-    }
-    if (c == 0) {
-      v = 40 + ((synth_vnoise(rx16, ry16, 4, o.seed) * 3 + synth_vnoise(rx16, ry16, 2, o.seed + 5)) >> 2) * 3 / 4;
-    } else {
-      v = 64 + (int)(synth_hash(k, c, f.seed) & 127) + (synth_vnoise(rx16, ry16, 5, o.seed + c) >> 3);
-    }
-  }
-  return v;
+struct SynthArgs {
+  SynthObject obj[kSynthObjects];  // depend on (seed, W, H) only
+  int32_t t[kMaxBatch];
+  int32_t ox[kMaxBatch][kSynthObjects], oy[kMaxBatch][kSynthObjects];  // per segment, after the bounce
+};
+static_assert(sizeof(SynthArgs) + sizeof(Geo) + sizeof(FrameSet) + 16 <= 4096, "kernel arguments are limited to 4 KB");
+
+// Table sizes: the coordinate span of a tile is (n - 1) * 16 on the luma grid, twice that for
+// the chroma planes.
+constexpr int kSynSpanX = (kSynTW - 1) * 16, kSynSpanY = (kSynTH - 1) * 16;
+constexpr int syn_max(int a, int b) { return a > b ? a : b; }
+constexpr int syn_pts(int lp, int s) { return synth_win_max(kSynSpanX << s, lp) * synth_win_max(kSynSpanY << s, lp); }
+constexpr int syn_rows(int lp, int s) { return synth_win_max(kSynSpanY << s, lp); }
+// background luma (lp 7, 5, 3 and the textured 1), object luma (4, 2), chroma (8; object 5)
+constexpr int syn_lat_size(bool tex) {
+  return syn_max(syn_max(syn_pts(7, 0) + syn_pts(5, 0) + syn_pts(3, 0) + (tex ? syn_pts(1, 0) : 0), syn_pts(4, 0) + syn_pts(2, 0)),
+                 syn_max(syn_pts(8, 1), syn_pts(5, 1)));
+}
+constexpr int syn_top_rows(bool tex) {
+  return syn_max(syn_max(syn_rows(7, 0) + syn_rows(5, 0) + syn_rows(3, 0) + (tex ? syn_rows(1, 0) : 0), syn_rows(4, 0) + syn_rows(2, 0)),
+                 syn_max(syn_rows(8, 1), syn_rows(5, 1)));
 }
 
-// kTex: the textured variant (seed bit 31) is a separate instantiation so the smooth source
-// keeps its register budget (a runtime branch doubled its time).  The objects are filtered
-// once per item by their vertical extent before the per-sample horizontal / shape tests.
-// (16 samples per item shared more cell hashes but cut occupancy 22 -> 13 waves/CU and was
-// 16 % slower: profiles/README.md.)
-template <bool kTex>
-__global__ void __launch_bounds__(256) k_synth(FrameSet src, Geo g, uint32_t seed, FrameIdx fi) {
-  const int c = blockIdx.y, b = blockIdx.z;
-  const int pw = c ? g.W / 2 : g.W, ph = c ? g.H / 2 : g.H;
-  const int dw = c ? g.dw / 2 : g.dw, dh = c ? g.dh / 2 : g.dh;
-  __shared__ SynthFrameCtx ctx;
-  if (threadIdx.x == 0) synth_frame_ctx(seed, fi.t[b], g.dw, g.dh, ctx);
-  __syncthreads();
-  uint8_t* P = src.plane(c, b, g);
-  const int s = c ? 1 : 0, pq = pw >> 2;  // pw is a multiple of 16
-  constexpr bool tex = kTex;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pq * ph; i += gridDim.x * blockDim.x) {
-    const int y = i / pq, x0 = (i - y * pq) * 4;
-    const int yc = tv_min(y, dh - 1), yl = yc << s;
-    const int32_t by16 = yl * 16 + ctx.t * (tex ? 36 : 12);
-    unsigned rows = 0;
+// Lattice of window w: wave r takes lattice rows r, r + 4, ..; a lane one point of the row.
+__device__ __forceinline__ void syn_lattice(const SynthWin& w, uint8_t* lat, int wave, int lane) {
+  for (int r = wave; r < w.npy; r += 4)
+    for (int i = lane; i < w.npx; i += 64) lat[r * w.npx + i] = (uint8_t)synth_win_lattice(w, i, r);
+}
+// Column `col` (coordinate p16, inside the window) of the window's top rows.
+__device__ __forceinline__ void syn_top(const SynthWin& w, const uint8_t* lat, uint16_t* top, int col, int32_t p16) {
+  int ci, sx;
+  synth_axis(p16, w.sh, w.cx0, ci, sx);
+  for (int r = 0; r < w.npy; ++r)
+    top[r * kSynTW + col] = (uint16_t)synth_top(lat[r * w.npx + ci], lat[r * w.npx + ci + 1], sx);
+}
+// The octave at the 4 samples from column x (a multiple of 4) of the row at coordinate p16.
+__device__ __forceinline__ void syn_eval(const SynthWin& w, const uint16_t* top, int x, int32_t p16, int n[4]) {
+  int cy, sy;
+  synth_axis(p16, w.sh, w.cy0, cy, sy);
+  const uint2 a = *reinterpret_cast<const uint2*>(top + cy * kSynTW + x);
+  const uint2 b = *reinterpret_cast<const uint2*>(top + (cy + 1) * kSynTW + x);
+  n[0] = synth_rows((int)(a.x & 0xffff), (int)(b.x & 0xffff), sy);
+  n[1] = synth_rows((int)(a.x >> 16), (int)(b.x >> 16), sy);
+  n[2] = synth_rows((int)(a.y & 0xffff), (int)(b.y & 0xffff), sy);
+  n[3] = synth_rows((int)(a.y >> 16), (int)(b.y >> 16), sy);
+}
+
+// One tile.  kTex: the textured variant (seed bit 31) adds the 2-pixel octave (more top rows of
+// LDS) and the per-sample grain hash.  kChroma: the chroma planes have one octave of their
+// own; a body per plane kind keeps the sample loops free of branches on the plane.
+template <bool kTex, bool kChroma>
+__device__ __forceinline__ void syn_tile(uint16_t* top, uint8_t* lat, FrameSet src, const Geo& g, uint32_t seed,
+                                         const SynthArgs& a, int c, int x0, int y0) {
+  constexpr int kBg = kChroma ? 1 : (kTex ? 4 : 3), kOb = kChroma ? 1 : 2, s = kChroma ? 1 : 0;
+  __builtin_assume(kChroma ? c != 0 : c == 0);
+  const int b = blockIdx.y;
+  const int pw = g.W >> s, ph = g.H >> s, dw = g.dw >> s, dh = g.dh >> s;
+  const int t = a.t[b];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // coordinate range of the tile, of this thread's table column and of its 4 sample columns
+  const int32_t tx0 = synth_tile_pos(x0, dw, s), tx1 = synth_tile_pos(x0 + kSynTW - 1, dw, s);
+  const int32_t ty0 = synth_tile_pos(y0, dh, s), ty1 = synth_tile_pos(y0 + kSynTH - 1, dh, s);
+  const int32_t colp = synth_tile_pos(x0 + tid, dw, s);
+  const int x = 4 * lane, yw = y0 + wave * kSynRows;
+  int32_t sp[4];
 #pragma unroll
-    for (int k = 0; k < kSynthObjects; ++k) {
-      const int32_t ry16 = yl * 16 - ctx.oy[k];
-      rows |= (ry16 >= 0 && ry16 < ctx.obj[k].h * 16) ? 1u << k : 0u;
-    }
-    VNoiseRow n0, n1, n2, n3;
-    if (c == 0) {
-      n0.init(by16, 7, ctx.seed);
-      n1.init(by16, 5, ctx.seed + 1);
-      n2.init(by16, 3, ctx.seed + 2);
-      if (tex) n3.init(by16, 1, ctx.seed + 3);
-    } else {
-      n0.init(by16, 8, ctx.seed + 10 * c);
-    }
-    uint32_t word = 0;
+  for (int j = 0; j < 4; ++j) sp[j] = synth_tile_pos(x0 + x + j, dw, s);
+
+  SynthWin w[kBg];
+  int lat0[kBg], row0[kBg];
+  const int panx = t * synth_pan_x(kTex), pany = t * synth_pan_y(kTex);
+  {
+    int lo = 0, ro = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int xc = tv_min(x0 + j, dw - 1), xl = xc << s;
-      const int32_t bx16 = xl * 16 + ctx.t * (tex ? 88 : 36);
-      int v;
-      if (c == 0 && tex)
-        v = (n0.eval(bx16) * 3 + n1.eval(bx16) * 2 + n2.eval(bx16) * 2 + n3.eval(bx16)) >> 3;
-      else if (c == 0)
-        v = (n0.eval(bx16) * 5 + n1.eval(bx16) * 2 + n2.eval(bx16)) >> 3;
-      else
-        v = 96 + (n0.eval(bx16) >> 1);
-      if (rows) v = synth_objects(ctx, c, xl, yl, v, rows);
-      if (tex) {  // per-frame grain, as synth_sample_ctx
-        const uint32_t gr = synth_hash(xc + ctx.t * 7919, yc + c * 104729, ctx.seed ^ 0x5bd1e995u);
-        v += c ? (int)(gr & 3) - 2 : (int)(gr & 7) - 4;
-      }
-      word |= (uint32_t)clip_pixel(v) << (8 * j);
+    for (int i = 0; i < kBg; ++i) {
+      w[i] = synth_win(synth_bg_lp(c, i), synth_bg_seed(seed, c, i), tx0 + panx, tx1 + panx, ty0 + pany, ty1 + pany);
+      lat0[i] = lo;
+      row0[i] = ro;
+      syn_lattice(w[i], lat + lo, wave, lane);
+      lo += w[i].npx * w[i].npy;
+      ro += w[i].npy;
     }
-    *reinterpret_cast<uint32_t*>(P + (long)y * pw + x0) = word;
   }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kBg; ++i) syn_top(w[i], lat + lat0[i], top + row0[i] * kSynTW, tid, colp + panx);
+  __syncthreads();
+  uint32_t word[kSynRows];  // every value before the grain is 0..255 (tv/synth.h)
+#pragma unroll
+  for (int j = 0; j < kSynRows; ++j) {
+    const int32_t py = synth_tile_pos(yw + j, dh, s) + pany;
+    int n[4][4] = {};
+#pragma unroll
+    for (int i = 0; i < kBg; ++i) syn_eval(w[i], top + row0[i] * kSynTW, x, py, n[i]);
+    word[j] = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int m[4] = {n[0][q], n[1][q], n[2][q], n[3][q]};
+      word[j] |= (uint32_t)synth_bg_mix(c, kTex, m) << (8 * q);
+    }
+  }
+
+  for (int k = 0; k < kSynthObjects; ++k) {  // later objects on top
+    const SynthObject& o = a.obj[k];
+    const int32_t ox = a.ox[b][k], oy = a.oy[b][k];
+    int32_t xlo, xhi, ylo, yhi;
+    synth_obj_range(tx0, tx1, ox, o.w, xlo, xhi);
+    synth_obj_range(ty0, ty1, oy, o.h, ylo, yhi);
+    if (xlo > xhi || ylo > yhi) continue;  // workgroup-uniform: the tile misses the bounding box
+    const int base = synth_obj_base(seed, k, c);
+    SynthWin wo[kOb];
+    int olat[kOb], orow[kOb];
+    __syncthreads();  // the tables are reused
+    {
+      int lo = 0, ro = 0;
+#pragma unroll
+      for (int i = 0; i < kOb; ++i) {
+        wo[i] = synth_win(synth_obj_lp(c, i), synth_obj_seed(o, c, i), xlo, xhi, ylo, yhi);
+        olat[i] = lo;
+        orow[i] = ro;
+        syn_lattice(wo[i], lat + lo, wave, lane);
+        lo += wo[i].npx * wo[i].npy;
+        ro += wo[i].npy;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kOb; ++i) syn_top(wo[i], lat + olat[i], top + orow[i] * kSynTW, tid, clip3(xlo, xhi, colp - ox));
+    __syncthreads();
+    int64_t cover[4];  // the shape test's column term; never passes outside the box
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int32_t rx16 = sp[q] - ox;
+      cover[q] = rx16 < xlo || rx16 > xhi ? INT64_MAX : synth_cover_col(o, rx16);
+    }
+#pragma unroll
+    for (int j = 0; j < kSynRows; ++j) {
+      const int32_t ry16 = synth_tile_pos(yw + j, dh, s) - oy;
+      if (ry16 < ylo || ry16 > yhi) continue;  // wave-uniform
+      const int64_t cover_row = synth_cover_row(o, ry16);
+      int n[2][4] = {};
+#pragma unroll
+      for (int i = 0; i < kOb; ++i) syn_eval(wo[i], top + orow[i] * kSynTW, x, ry16, n[i]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (cover[q] > cover_row) continue;
+        const int m[2] = {n[0][q], n[1][q]};
+        word[j] = (word[j] & ~(0xffu << (8 * q))) | (uint32_t)synth_obj_mix(c, base, m) << (8 * q);
+      }
+    }
+  }
+
+  if (x0 + x >= pw) return;
+  uint8_t* P = src.plane(c, b, g);
+#pragma unroll
+  for (int j = 0; j < kSynRows; ++j) {
+    const int y = yw + j;
+    if (y >= ph) break;
+    uint32_t out = word[j];
+    if (kTex) {  // per-frame grain at the clamped position, as synth_sample_ctx
+      const int yc = tv_min(y, dh - 1);
+      out = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int v = (int)((word[j] >> (8 * q)) & 255) + synth_grain(seed, t, c, tv_min(x0 + x + q, dw - 1), yc);
+        out |= (uint32_t)clip_pixel(v) << (8 * q);
+      }
+    }
+    *reinterpret_cast<uint32_t*>(P + (long)y * pw + x0 + x) = out;
+  }
+}
+
+template <bool kTex>
+__global__ void __launch_bounds__(256) k_synth(FrameSet src, Geo g, uint32_t seed, SynthArgs a) {
+  __shared__ __attribute__((aligned(8))) uint16_t top[syn_top_rows(kTex) * kSynTW];
+  __shared__ uint8_t lat[syn_lat_size(kTex)];
+  // blockIdx.x: the luma tiles, then the U and the V tiles, row-major
+  const int nlx = (g.W + kSynTW - 1) / kSynTW, ncx = (g.W / 2 + kSynTW - 1) / kSynTW;
+  const int nl = nlx * ((g.H + kSynTH - 1) / kSynTH), nc = ncx * ((g.H / 2 + kSynTH - 1) / kSynTH);
+  int id = blockIdx.x, c = 0;
+  if (id >= nl) {
+    c = id >= nl + nc ? 2 : 1;
+    id -= nl + (c - 1) * nc;
+  }
+  const int ntx = c ? ncx : nlx, ty = id / ntx, x0 = (id - ty * ntx) * kSynTW, y0 = ty * kSynTH;
+  if (c)
+    syn_tile<kTex, true>(top, lat, src, g, seed, a, c, x0, y0);
+  else
+    syn_tile<kTex, false>(top, lat, src, g, seed, a, 0, x0, y0);
 }
 
 // ------------------------------------------ SSE -----------------------------------------
@@ -414,12 +505,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 }
 
 // ------------------------------------ launchers -----------------------------------------
+// The frame contexts travel as kernel arguments (the QpArgs precedent below): the objects
+// depend on (seed, W, H) only, a segment adds its frame time and the objects' positions.
 void launch_synth(FrameSet src, const Geo& g, uint32_t seed, const FrameIdx& fi, int B, hipStream_t s) {
-  dim3 grid((unsigned)tv_min(512, (int)((g.ysz + 1023) / 1024)), 3, B);
+  SynthArgs a;
+  std::memset(&a, 0, sizeof a);
+  SynthFrameCtx f;
+  for (int b = 0; b < B; ++b) {
+    synth_frame_ctx(seed, fi.t[b], g.dw, g.dh, f);
+    a.t[b] = f.t;
+    std::memcpy(a.ox[b], f.ox, sizeof f.ox);
+    std::memcpy(a.oy[b], f.oy, sizeof f.oy);
+  }
+  if (B > 0) std::memcpy(a.obj, f.obj, sizeof f.obj);
+  auto tiles = [](int w, int h) { return ((w + kSynTW - 1) / kSynTW) * ((h + kSynTH - 1) / kSynTH); };
+  dim3 grid((unsigned)(tiles(g.W, g.H) + 2 * tiles(g.W / 2, g.H / 2)), (unsigned)B);
   if (synth_textured(seed))
-    k_synth<true><<<grid, 256, 0, s>>>(src, g, seed, fi);
+    k_synth<true><<<grid, 256, 0, s>>>(src, g, seed, a);
   else
-    k_synth<false><<<grid, 256, 0, s>>>(src, g, seed, fi);
+    k_synth<false><<<grid, 256, 0, s>>>(src, g, seed, a);
 }
 // One picture of B device-resident segments ([segment][frame][Y | U | V] at the coded size,
 // segment stride seg_stride bytes) into the B source planes: one launch instead of 3 B

@@ -35,6 +35,7 @@ CORE = {
     "tv_bytes_data": (vp, [vp]),
     "tv_bytes_clear": (None, [vp]),
     "tv_synth_frame": (None, [u32, i, i, i, u8p, u8p, u8p]),
+    "tv_synth_frame_tiled": (None, [u32, i, i, i, i, i, u8p, u8p, u8p]),
     "tv_satd8x8": (i, [i32p, i]),
     # HEVC golden encoder
     "tv_cpu_encoder_new": (vp, [i] * 6),
