@@ -1879,7 +1879,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
     fd.fp.qindex = qidx;
     const int lvl = (dbg & 1) ? 0 : lf_level_for_q(qidx);
     for (int i = 0; i < 4; ++i) fd.fp.lf[i] = lvl;
-    fd.fp.cdef_damping = 3 + (qidx0 >> 6);  // per stream (the engine's CDEF launches take one damping)
+    fd.fp.cdef_damping = cdef_damping_for_q(qidx0);  // per stream (the engine's CDEF launches take one damping)
     fd.mode.assign(nb, 0);
     fd.mv.assign(nb, 0);
     fd.ly.assign((size_t)nb * 256, 0);
@@ -2300,29 +2300,32 @@ const char* tv_av1c_last_error() { return g_codec_err.c_str(); }
 // Dc_Qlookup / Ac_Qlookup (8-bit) of q-index q (dc != 0: the DC table)
 int tv_av1c_qlookup(int q, int dc) { return dc ? dc_q(q) : ac_q(q); }
 
-int tv_av1c_golden_encode_tools(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, int tools,
-                                void* out, int64_t* tu_sizes, uint8_t* recon, uint32_t* mode, uint32_t* mv,
-                                int16_t* ly, int16_t* lu, int16_t* lv, int32_t* fparams, int8_t* cdef, int32_t* lr,
-                                uint8_t* ib);
+// Encoder model constants (av1_enc.h) for the GPU engine's host side.  out [6 + kNumLrSets] =
+// kCdefMaskY, kCdefMaskUV, kMvMemoRecordBytes, kIbPasses, kToolIntraInInter, kToolCfl, then
+// the lr_set() values; returns kNumLrSets.
+int tv_av1c_model_constants(int64_t* out) {
+  const int64_t c[6] = {(int64_t)kCdefMaskY, (int64_t)kCdefMaskUV, kMvMemoRecordBytes, kIbPasses, kToolIntraInInter,
+                        kToolCfl};
+  for (int i = 0; i < 6; ++i) out[i] = c[i];
+  for (int k = 0; k < kNumLrSets; ++k) out[6 + k] = lr_set(k);
+  return kNumLrSets;
+}
+// Per-q-index model values: out [3] = lf_level_for_q, lr_rate_cost, cdef_damping_for_q.
+void tv_av1c_model_q(int q, int64_t* out) {
+  out[0] = lf_level_for_q(q);
+  out[1] = lr_rate_cost(q);
+  out[2] = cdef_damping_for_q(q);
+}
 
 // Golden encode of n coded-size I420 frames (concatenated Y U V per frame) at `qidx`:
 // the temporal units go to `out` (one Bytes object) and their byte sizes to tu_sizes[n];
 // the post-filter reconstructions to recon (same layout); per-frame decisions to mode /
 // mv [n][nblk] and levels ly [n][nblk][256], lu / lv [n][nblk][64] (may be null).
-int tv_av1c_golden_encode(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, void* out,
-                          int64_t* tu_sizes,
-                          uint8_t* recon, uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv,
-                          int32_t* fparams, int8_t* cdef, int32_t* lr) {
-  return tv_av1c_golden_encode_tools(dw, dh, n, yuv, qidx, qmap, 0, out, tu_sizes, recon, mode, mv, ly, lu, lv, fparams,
-                                     cdef, lr, nullptr);
-}
-
-// The same with a coding-tools word (av1_enc.h: bit 0 kToolIntraInInter); ib [n][nblk]
-// (may be null): per frame and block, bit 0 = intra candidate, bit 1 = accepted.
-int tv_av1c_golden_encode_tools(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, int tools,
-                                void* out, int64_t* tu_sizes, uint8_t* recon, uint32_t* mode, uint32_t* mv,
-                                int16_t* ly, int16_t* lu, int16_t* lv, int32_t* fparams, int8_t* cdef, int32_t* lr,
-                                uint8_t* ib) {
+// tools: the coding-tools word (av1_enc.h kToolIntraInInter, kToolCfl); ib [n][nblk] (may be
+// null): per frame and block, bit 0 = intra candidate, bit 1 = accepted.
+int tv_av1c_golden_encode(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, int tools, void* out,
+                          int64_t* tu_sizes, uint8_t* recon, uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu,
+                          int16_t* lv, int32_t* fparams, int8_t* cdef, int32_t* lr, uint8_t* ib) {
   return codec_guard([&] {
     const SeqGeo g = make_seq_geo(dw, dh);
     const size_t fsz = (size_t)g.W * g.H * 3 / 2;

@@ -819,10 +819,6 @@ int tv_gpu_av1_deblock_step(const uint8_t* in, uint8_t* out, int w, int h, int B
                                                                                                   estep);
   return av1_status("av1_deblock");
 }
-int tv_gpu_av1_deblock(const uint8_t* in, uint8_t* out, int w, int h, int B, int chroma, const uint32_t* info,
-                       int sharp, void* stream) {
-  return tv_gpu_av1_deblock_step(in, out, w, h, B, chroma, info, sharp, 4, stream);
-}
 int tv_gpu_sgr_apply(const uint8_t* rec, int w, int h, int B, const int* params, uint8_t* out, void* stream) {
   if (bad_geo(w, h, B, 2, "sgr_apply")) return -1;
   k_sgr<false><<<dim3(nunits(w, h), B), 256, 0, (hipStream_t)stream>>>(nullptr, rec, w, h, 0, params, nullptr, out);

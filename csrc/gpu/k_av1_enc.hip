@@ -1116,18 +1116,6 @@ __global__ void __launch_bounds__(kCcT) k_av1e_cdef_choose(const unsigned long l
   }
 }
 
-// ================================================================= loop restoration =====
-// per (segment, unit): projection weights of parameter set `set` from sgr_stats
-__global__ void k_av1e_lr_solve(const long long* __restrict__ st, int nu, int B, int set, int* __restrict__ prm) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nu * B) return;
-  int x0, x1;
-  sgr_solve(st + 5L * i, sgr_param(set, 0), sgr_param(set, 2), &x0, &x1);
-  prm[3L * i] = set;
-  prm[3L * i + 1] = x0;
-  prm[3L * i + 2] = x1;
-}
-
 // per (64x64 unit, segment): SSE of two planes over the valid region [0, vw) x [0, vh)
 __global__ void __launch_bounds__(256) k_av1e_unit_sse(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                                                        int w, int h, int vw, int vh, long long* __restrict__ out) {
@@ -1250,11 +1238,12 @@ const char* tv_av1e_last_error() { return g_err.c_str(); }
 // P frame of B segments: src / ref / rec planes [B][H][W] (+ chroma [B][H/2][W/2]); qarr:
 // device q-index per segment (1..255, range-checked by the host engine).  The motion field
 // goes through `tmp` ([B][nb] words): search -> tmp, kMvRefineRounds refinement rounds
-// ping-ponging between tmp and mv (ending in mv), then the recon at mv.
-static int inter_frame(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
-                       const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv,
-                       uint32_t* tmp, unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu,
-                       int16_t* lv, int* icost, int W, int H, int B, const int* qarr, void* stream) {
+// ping-ponging between tmp and mv (ending in mv), then the recon at mv.  icost (may be null):
+// [B][nb], every block's inter cost (luma SATD at its final MV), the input of tv_av1e_iblocks.
+int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
+                  const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv, uint32_t* tmp,
+                  unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu, int16_t* lv, int* icost,
+                  int W, int H, int B, const int* qarr, void* stream) {
   if (bad(W, H, B, 1, "av1e_inter") || ensure_tables()) return -1;
   static_assert(kMvRefineRounds % 2 == 1, "an odd round count ends the field in `mv`");
   const int nb = (W >> 4) * (H >> 4), nsb = ((W + 63) >> 6) * ((H + 63) >> 6);
@@ -1265,7 +1254,7 @@ static int inter_frame(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, 
   const long nrec = (long)B * nb;
   MvMemo mm[2];
   for (int k = 0; k < 2; ++k) {
-    uint8_t* base = memo + k * nrec * (kMvRefineMaxCand * 8 + 1);
+    uint8_t* base = memo + k * nrec * kMvMemoRecordBytes;
     mm[k].mv = reinterpret_cast<uint32_t*>(base);
     mm[k].sat = reinterpret_cast<int*>(base + nrec * kMvRefineMaxCand * 4);
     mm[k].n = base + nrec * kMvRefineMaxCand * 8;
@@ -1287,37 +1276,15 @@ static int inter_frame(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, 
   return status("av1e_inter");
 }
 
-int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
-                  const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv, uint32_t* tmp,
-                  unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H,
-                  int B, const int* qarr, void* stream) {
-  return inter_frame(sy, su, sv, ry, ru, rv, oy, ou, ov, mode, mv, tmp, satd_acc, memo, ly, lu, lv, nullptr, W, H, B,
-                     qarr, stream);
-}
-
-// tv_av1e_inter that also writes every block's inter cost (luma SATD at its final MV) to
-// icost [B][nb], the input of tv_av1e_iblocks.
-int tv_av1e_inter_cost(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
-                       const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv,
-                       uint32_t* tmp, unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu,
-                       int16_t* lv, int* icost, int W, int H, int B, const int* qarr, void* stream) {
-  if (!icost) {
-    g_err = "av1e_inter_cost: no cost buffer";
-    return -1;
-  }
-  return inter_frame(sy, su, sv, ry, ru, rv, oy, ou, ov, mode, mv, tmp, satd_acc, memo, ly, lu, lv, icost, W, H, B,
-                     qarr, stream);
-}
-
-// Intra blocks of an inter frame (tv/av1_enc.h), between tv_av1e_inter_cost and tv_av1e_merge:
+// Intra blocks of an inter frame (tv/av1_enc.h), between tv_av1e_inter and tv_av1e_merge:
 // o* / mode / mv / l* are the frame's reconstruction and decisions (accepted blocks are
-// overwritten); icost [B][nb] from tv_av1e_inter_cost; scratch cand [B][nb] bytes, cnt
+// overwritten); icost [B][nb] from tv_av1e_inter; scratch cand [B][nb] bytes, cnt
 // [B][7] ints, list [B][7][nb] words; ib [B][nb]: bit 0 candidate, bit 1 accepted.
 // tools: the coding-tools word (kToolCfl: the accepted blocks also try chroma from luma).
-int tv_av1e_iblocks_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou,
-                          uint8_t* ov, uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv,
-                          const int* icost, uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B,
-                          const int* qarr, int tools, void* stream) {
+int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
+                    uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, const int* icost,
+                    uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B, const int* qarr,
+                    int tools, void* stream) {
   if (bad(W, H, B, 1, "av1e_iblocks") || ensure_tables()) return -1;
   const int nb = (W >> 4) * (H >> 4);
   hipStream_t st = (hipStream_t)stream;
@@ -1332,19 +1299,12 @@ int tv_av1e_iblocks_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* s
                                         cnt, list, pass);
   return status("av1e_iblocks");
 }
-int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
-                    uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, const int* icost,
-                    uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B, const int* qarr,
-                    void* stream) {
-  return tv_av1e_iblocks_tools(sy, su, sv, oy, ou, ov, mode, mv, ly, lu, lv, icost, cand, ib, cnt, list, W, H, B, qarr,
-                               0, stream);
-}
 
 // Key frame of B segments: one launch per anti-diagonal of the 16x16 block grid.
 // tools: the coding-tools word (kToolCfl: every block also tries chroma from luma).
-int tv_av1e_intra_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
-                        uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H, int B,
-                        const int* qarr, int tools, void* stream) {
+int tv_av1e_intra(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
+                  uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H, int B,
+                  const int* qarr, int tools, void* stream) {
   if (bad(W, H, B, 1, "av1e_intra") || ensure_tables()) return -1;
   const int bw = W >> 4, bh = H >> 4;
   const auto intra = (tools & kToolCfl) ? k_av1e_intra<true> : k_av1e_intra<false>;
@@ -1354,11 +1314,6 @@ int tv_av1e_intra_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* sv,
                                                                 ly, lu, lv, W, H, qarr, d, lo);
   }
   return status("av1e_intra");
-}
-int tv_av1e_intra(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
-                  uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H, int B,
-                  const int* qarr, void* stream) {
-  return tv_av1e_intra_tools(sy, su, sv, oy, ou, ov, mode, mv, ly, lu, lv, W, H, B, qarr, 0, stream);
 }
 
 // flag the 8x8 blocks of skip blocks in dir [B][n8] (after tv_gpu_cdef_dirs)
@@ -1409,16 +1364,6 @@ int tv_av1e_lfinfo(const uint32_t* mode, int W, int H, int B, const int* lvl, ui
   const int n = (W >> 2) * (H >> 2);
   k_av1e_lfinfo<<<dim3((n + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(mode, W, H, lvl, iy, iu, iv);
   return status("av1e_lfinfo");
-}
-
-// st [B][nu][5] (tv_gpu_sgr_stats) -> prm [B][nu][3] = (set, xqd0, xqd1)
-int tv_av1e_lr_solve(const long long* st, int nu, int B, int set, int* prm, void* stream) {
-  if (nu < 1 || B < 1 || set < 0 || set > 15) {
-    g_err = "av1e_lr_solve: bad arguments";
-    return -1;
-  }
-  k_av1e_lr_solve<<<(nu * B + 255) / 256, 256, 0, (hipStream_t)stream>>>(st, nu, B, set, prm);
-  return status("av1e_lr_solve");
 }
 
 // out [B][units]: per-64x64-unit SSE of a / b ([B][h][w]) over the valid region vw x vh

@@ -297,6 +297,8 @@ constexpr uint64_t cdef_mask(const int* pri, int npri, const int* sec, int nsec)
 constexpr int kCdefPriY[8] = {0, 1, 2, 3, 5, 7, 10, 13}, kCdefPriUV[4] = {0, 2, 4, 7}, kCdefSec[2] = {0, 2};
 constexpr uint64_t kCdefMaskY = cdef_mask(kCdefPriY, 8, kCdefSec, 2);
 constexpr uint64_t kCdefMaskUV = cdef_mask(kCdefPriUV, 4, kCdefSec, 2);
+// cdef_damping of a stream, from its base q-index (3..6)
+TV_HD int cdef_damping_for_q(int q) { return 3 + (q >> 6); }
 
 // ---------------------------------------------------------------- loop restoration ------
 // Self-guided restoration (SGRPROJ) per 64x64 unit of each plane: candidate parameter sets
@@ -372,6 +374,9 @@ TV_HD int me_ring_dy(int k) { constexpr int8_t t[8] = {-1, -1, -1, 0, 0, 1, 1, 1
 // the independent per-block search (tools/rd_curve.py --codec av1, profiles/README.md).
 constexpr int kMvRefineRounds = 3;
 constexpr int kMvRefineMaxCand = 11;
+// bytes of one block's record in the GPU's refinement memo: kMvRefineMaxCand MV words and as
+// many SATDs, and a count
+constexpr int kMvMemoRecordBytes = kMvRefineMaxCand * 8 + 1;
 // candidate list of block (bx, by) from the current field `cur` (bw x bh blocks):
 // own, left, above, above-right, right, below, zero, then the distance-2 neighbours
 // (left, above, right, below); duplicates dropped.  Returns the count.

@@ -94,7 +94,7 @@ def test_parser_handles_the_forms_in_use():
     assert core["tv_mux_mp4_file"][1][0] == "uint8_t**"  # const T* const*
     assert "unsigned long long" in gpu["tv_gpu_cdef_search"][1]
     assert core["tv_mux_file"][1].count("SideTrack*") == 1
-    assert len(gpu["tv_av1e_inter"][1]) == 22  # multi-line parameter list
+    assert len(gpu["tv_av1e_inter"][1]) == 23  # multi-line parameter list
 
 
 def test_parser_sees_every_exported_symbol():

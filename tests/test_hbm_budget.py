@@ -1,6 +1,6 @@
-"""HBM-aware engine sizing (verdict r3 item 8): the native footprint ledger and its
-no-allocation estimate, the byte-budgeted EngineCache (LRU eviction by bytes) and the
-budget-capped auto_batch."""
+"""HBM-aware engine sizing (verdict r3 item 8): the engines' footprint ledgers (the HEVC
+engine's native one, the AV1 engine's buffer declaration) and their no-allocation estimates,
+the byte-budgeted EngineCache (LRU eviction by bytes) and the budget-capped auto_batch."""
 import pytest
 
 from thinvids_amd.worker.encoder import EncodeSpec, EngineCache, auto_batch, engine_bytes
@@ -18,6 +18,43 @@ def test_estimate_scales_with_batch_sao_and_dpb():
     assert estimate_footprint(1920, 1080, 48, 64, bframes=8)["dev"] > b  # a deeper DPB
     assert 3 * GiB < b < 8 * GiB  # 1080p x 48: the measured order of magnitude
     assert estimate_footprint(3840, 2160, 24, 64)["dev"] > 1.9 * a
+
+
+def test_av1_estimate_scales_with_batch_tool_and_gop():
+    from thinvids_amd.models.av1_engine import Av1GpuEngine
+
+    est = lambda *a, **k: Av1GpuEngine.estimate(*a, **k)["dev"]
+    a, b = est(1920, 1080, 16, 64), est(1920, 1080, 32, 64)
+    assert 1.9 < b / a < 2.05  # every buffer is per segment
+    assert est(1920, 1080, 32, 64, intra_in_inter=True) > b  # the intra-block scratch and the slots' maps
+    assert est(1920, 1080, 32, 1) < est(1920, 1080, 32, 2) < est(1920, 1080, 32, 63) < b  # the GOP slots
+    assert engine_bytes(EncodeSpec(1920, 1080, gop=64, codec="av1"), 32) > b  # plus the staging buffer
+
+
+def test_av1_estimate_is_the_sum_of_the_declared_buffers():
+    """Display 72x40 -> coded 80x48, batch 3, GOP 3, every buffer of the declaration by hand."""
+    from thinvids_amd.models.av1_engine import Av1GpuEngine
+
+    W, H, B, F = 80, 48, 3, 3
+    nb, n8, nfb = 5 * 3, 10 * 6, 2 * 1  # 16x16 blocks, 8x8 blocks, 64x64 filter blocks
+    planes = W * H + 2 * (W // 2) * (H // 2)  # one I420 plane set, bytes
+    work = (5 * planes  # src, rec, fin, deblocked, CDEF output
+            + 4 * ((W // 4) * (H // 4) + 2 * (W // 8) * (H // 8))  # iy, iu, iv words
+            + n8 + 4 * n8  # dirs bytes, var words
+            + 3 * nfb * 64 * 8  # three CDEF SSE tables
+            + 2 * nfb  # py, puv
+            + 3 * 1 * 3 * 4  # prm: one restoration unit per plane, three words
+            + 8 * (2 + 1 + 1)  # per-unit SSE: 2 luma units (ceil), 1 per chroma plane
+            + 4 * nb + 8 + 2 * nb * 89)  # mvtmp, satd, two memo record sets of 11 * 8 + 1 bytes
+    ib_work = 4 * nb + nb + 4 * 7 + 4 * 7 * nb  # ibcost, ibcand, ibcnt, iblist (7 passes)
+    slot = F * B * (4 * nb + 4 * nb  # mode, mv
+                    + 2 * nb * (256 + 64 + 64)  # levels
+                    + 16 + nfb + 3 * 8  # tabs, fbidx, sse
+                    + 3 * 1 * 3 * 4)  # lr: 3 planes x 1 unit x 3 words
+    upload = F * B * (4 + 4 * 4 + 8)  # q-index, four filter levels, restoration rate
+    assert Av1GpuEngine.estimate(72, 40, B, F)["dev"] == B * work + 2 * slot + upload == 320442
+    assert Av1GpuEngine.estimate(72, 40, B, F, intra_in_inter=True)["dev"] == (
+        B * (work + ib_work) + 2 * (slot + F * B * nb) + upload)
 
 
 class _FakeEngine:

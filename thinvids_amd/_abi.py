@@ -84,10 +84,10 @@ CORE = {
     # AV1 codec golden model
     "tv_av1c_last_error": (cstr, []),
     "tv_av1c_qlookup": (i, [i, i]),
-    "tv_av1c_golden_encode": (i, [i, i, i, u8p, i, i32p, vp, i64p, u8p, u32p, u32p, i16p, i16p, i16p, i32p, i8p,
-                                  i32p]),
-    "tv_av1c_golden_encode_tools": (i, [i, i, i, u8p, i, i32p, i, vp, i64p, u8p, u32p, u32p, i16p, i16p, i16p, i32p,
-                                        i8p, i32p, u8p]),
+    "tv_av1c_model_constants": (i, [i64p]),
+    "tv_av1c_model_q": (None, [i, i64p]),
+    "tv_av1c_golden_encode": (i, [i, i, i, u8p, i, i32p, i, vp, i64p, u8p, u32p, u32p, i16p, i16p, i16p, i32p, i8p,
+                                  i32p, u8p]),
     "tv_av1c_ib_accept": (i, [u8p, i, i, u8p]),
     "tv_av1c_cfl_decide": (i, [u8p, u8p, u8p, i, i, i, i, i32p]),
     "tv_av1c_decode": (i, [u8p, sz, i, u8p, i32p, i32p]),
@@ -171,23 +171,18 @@ GPU = {
     "tv_gpu_sgr_stats": (i, [vp, vp, i, i, i, i, vp, vp]),
     "tv_gpu_sgr_apply": (i, [vp, i, i, i, vp, vp, vp]),
     "tv_gpu_av1_deblock_step": (i, [vp, vp, i, i, i, i, vp, i, i, vp]),
-    "tv_gpu_av1_deblock": (i, [vp, vp, i, i, i, i, vp, i, vp]),
     "tv_av1_txfm_last_error": (cstr, []),
     "tv_gpu_av1_txfm": (i, [vp, vp, i, i, i, vp, vp, vp]),
     # k_av1_enc.hip: the AV1 engine (device pointers, stream last)
     "tv_av1e_last_error": (cstr, []),
-    "tv_av1e_inter": (i, [vp] * 17 + [i, i, i, vp, vp]),
-    "tv_av1e_inter_cost": (i, [vp] * 18 + [i, i, i, vp, vp]),
-    "tv_av1e_iblocks": (i, [vp] * 16 + [i, i, i, vp, vp]),
-    "tv_av1e_iblocks_tools": (i, [vp] * 16 + [i, i, i, vp, i, vp]),
-    "tv_av1e_intra": (i, [vp] * 11 + [i, i, i, vp, vp]),
-    "tv_av1e_intra_tools": (i, [vp] * 11 + [i, i, i, vp, i, vp]),
+    "tv_av1e_inter": (i, [vp] * 18 + [i, i, i, vp, vp]),
+    "tv_av1e_iblocks": (i, [vp] * 16 + [i, i, i, vp, i, vp]),
+    "tv_av1e_intra": (i, [vp] * 11 + [i, i, i, vp, i, vp]),
     "tv_av1e_cdef_skip": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_merge": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_tb_len": (i, [vp, vp, l, i, i, i, i, vp, vp]),
     "tv_av1e_tb_pack": (i, [vp, vp, vp, l, i, i, i, i, vp, vp]),
     "tv_av1e_lfinfo": (i, [vp, i, i, i, vp, vp, vp, vp, vp]),
-    "tv_av1e_lr_solve": (i, [vp, i, i, i, vp, vp]),
     "tv_av1e_unit_sse": (i, [vp, vp, i, i, i, i, i, vp, vp]),
     "tv_av1e_cdef_choose": (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]),
 }

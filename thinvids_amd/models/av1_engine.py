@@ -17,6 +17,12 @@ stay resident in HBM; at the end of the GOP the nonzero transform blocks are com
 the device and copied to the host once, and a CPU thread pool writes every segment's OBU
 temporal units (range coder) while the GPU moves on to the next GOP.
 
+Device memory: `buffers()` below names every device buffer of an engine once; the
+constructor and `_alloc_gop` allocate from it, `Av1GpuEngine.estimate` sums it without a GPU
+(the worker's byte budget, worker/encoder.py engine_bytes) and `footprint()` sums what was
+allocated.  A frame allocates nothing.  The encoder model's constants and per-q-index values
+(av1_enc.h) are read from the core library, not restated here.
+
 Bit-exact with the C++ golden encoder (``av1.golden_encode``), whose streams decode
 bit-exactly with dav1d (tests/test_av1_conformance.py), and with the decoder oracle
 (``av1.decode``): tests/test_av1_codec.py.
@@ -24,29 +30,36 @@ bit-exactly with dav1d (tests/test_av1_conformance.py), and with the decoder ora
 from __future__ import annotations
 
 import concurrent.futures as cf
+import ctypes as C
 import os
 from dataclasses import dataclass
 
 import numpy as np
 
-from .._native import dptr as _p, gpu_lib as _gpu, ok, stream
+from .._native import core_lib as _core, dptr as _p, gpu_lib as _gpu, ok, stream
 from . import av1 as av1m
 
 
-def _cdef_mask(pri, sec) -> int:
-    return sum(1 << (p * 4 + s) for p in pri for s in sec)
+def _model():
+    """The encoder model of csrc/include/tv/av1_enc.h, read from the core library once:
+    constants, and the per-q-index tables of q = 0..255."""
+    lib = _core()
+    c = (C.c_int64 * 16)()
+    nsets = lib.tv_av1c_model_constants(c)
+    q = np.zeros((256, 3), np.int64)
+    for i in range(256):
+        lib.tv_av1c_model_q(i, q[i].ctypes.data_as(C.POINTER(C.c_int64)))
+    return list(c[:6]) + [tuple(c[6:6 + nsets])], q
 
 
-# evaluated CDEF presets: av1_enc.h kCdefMaskY / kCdefMaskUV
-CDEF_MASK_Y = _cdef_mask((0, 1, 2, 3, 5, 7, 10, 13), (0, 2))
-CDEF_MASK_UV = _cdef_mask((0, 2, 4, 7), (0, 2))
+(CDEF_MASK_Y, CDEF_MASK_UV, MEMO_RECORD_BYTES, IB_PASSES, TOOL_INTRA_IN_INTER, TOOL_CFL, LR_SETS), _Q = _model()
+LF_LEVEL = _Q[:, 0].astype(np.int32)  # frame loop-filter level of a q-index
+LR_RATE = _Q[:, 1].copy()  # rate of a restored unit in SSE units
+CDEF_DAMPING = _Q[:, 2].astype(np.int32)  # of a stream, from its base q-index
 
 
 def _ok(rc: int):
     ok(rc, _gpu(), "tv_av1e_last_error")
-
-
-LR_SETS = (4, 10)  # av1_enc.h lr_set()
 
 
 def lr_grid(size: int) -> int:
@@ -54,15 +67,55 @@ def lr_grid(size: int) -> int:
     return max(1, (size + 32) // 64)
 
 
-def lr_rate_cost(q: int) -> int:
-    """Rate of a restored unit in SSE units (av1_enc.h lr_rate_cost)."""
-    a = av1m.ac_q(q)
-    return ((a * a * 9) >> 10) * 16
+def buffers(W: int, H: int, B: int, F: int, intra_in_inter: bool = False) -> dict:
+    """Every device buffer of an engine of coded size W x H, B segments and GOPs of up to F
+    frames, as group -> name -> (shape, dtype name):
+
+    * ``work``: the frame workspace, allocated by the constructor.  Kernels run on the
+      ``[:nseg]`` leading views of these full-batch buffers.
+    * ``slot``: one GOP decision slot; the engine holds two (_alloc_gop).
+    * ``upload``: the per-GOP q-index / filter-level / restoration-rate uploads.
+
+    Aliasing: k_deblock, k_cdef_apply and k_sgr_select read neighbouring tiles of their
+    inputs, so an output buffer is never one of that launch's inputs (rec -> dbk -> cdf ->
+    fin).  The reference (`fin` of frame t-1) is read by k_av1e_inter and the refine / unify
+    kernels of frame t and by nothing later, so the last filter of frame t (the restoration,
+    or the CDEF apply without it) writes `fin` in the same stream.  The copy stream reads GOP
+    slots only, never the workspace."""
+    bw, bh = W // 16, H // 16
+    nb, n8, nfb = bw * bh, (W // 8) * (H // 8), -(-W // 64) * -(-H // 64)
+    planes = (("y", H, W), ("u", H // 2, W // 2), ("v", H // 2, W // 2))
+    work = {f"{s}_{c}": ((B, h, w), "uint8") for s in ("src", "rec", "fin", "dbk", "cdf") for c, h, w in planes}
+    work.update({
+        "iy": ((B, H // 4, W // 4), "int32"),
+        "iu": ((B, H // 8, W // 8), "int32"), "iv": ((B, H // 8, W // 8), "int32"),
+        "dirs": ((B, n8), "uint8"), "var": ((B, n8), "int32"),
+        "se_y": ((B, nfb, 64), "int64"), "se_u": ((B, nfb, 64), "int64"), "se_v": ((B, nfb, 64), "int64"),
+        "py": ((B, nfb), "int8"), "puv": ((B, nfb), "int8"),
+    })
+    for c, h, w in planes:
+        work[f"prm_{c}"] = ((B, lr_grid(w) * lr_grid(h), 3), "int32")
+        work[f"sse_{c}"] = ((B, -(-h // 64) * -(-w // 64)), "int64")
+    # inter frames: the motion field's second buffer, per-segment frame SATD, two [B][nb] memo record sets
+    work.update({"mvtmp": ((B, nb), "int32"), "satd": ((B,), "int64"),
+                 "memo": ((2 * B * nb * MEMO_RECORD_BYTES,), "uint8")})
+    if intra_in_inter:  # scratch of the intra-block passes
+        work.update({"ibcost": ((B, nb), "int32"), "ibcand": ((B, nb), "uint8"), "ibcnt": ((B, IB_PASSES), "int32"),
+                     "iblist": ((B, IB_PASSES, nb), "int32")})
+    slot = {
+        "mode": ((F, B, nb), "int32"), "mv": ((F, B, nb), "int32"),
+        "ly": ((F, B, nb, 256), "int16"), "lu": ((F, B, nb, 64), "int16"), "lv": ((F, B, nb, 64), "int16"),
+        "tabs": ((F, B, 16), "uint8"), "fbidx": ((F, B, nfb), "int8"), "sse": ((F, B, 3), "int64"),
+        "lr": ((F, B, 3, av1m.lr_units(W, H), 3), "int32"),
+    }
+    if intra_in_inter:
+        slot["ib"] = ((F, B, nb), "uint8")
+    upload = {"q": ((F, B), "int32"), "lf": ((F, B, 4), "int32"), "lr_rate": ((F, B), "int64")}
+    return {"work": work, "slot": slot, "upload": upload}
 
 
-def lf_level(q: int) -> int:
-    """Frame loop-filter level of a q-index (av1_enc.h lf_level_for_q)."""
-    return min(63, max(0, (av1m.ac_q(q) * 20723 + 1015158) >> 18))
+def _nbytes(group: dict) -> int:
+    return sum(int(np.prod(shape)) * np.dtype(dt).itemsize for shape, dt in group.values())
 
 
 @dataclass
@@ -96,57 +149,51 @@ class Av1GpuEngine:
 
         self.intra_in_inter = bool(intra_in_inter)
         self.cfl = bool(cfl)
-
+        self.tools = TOOL_CFL if self.cfl else 0  # the kernels' tools word (intra_in_inter is a launch of its own)
         self.cascade = bool(cascade)  # constant q: the low-delay q cascade (av1.cascade_qmap)
         self.torch = torch
         self.w, self.h, self.B, self.q = width, height, batch, int(qindex)
         self.W, self.H = av1m.coded_size(width, height)
         self.dev = torch.device("cuda", device)
-        self.nb = (self.W // 16) * (self.H // 16)
-        self.nfb = ((self.W + 63) // 64) * ((self.H + 63) // 64)
-        self.nu = av1m.lr_units(self.W, self.H)
         self.lr_enabled = True
-        self.lvl = self._lf_level()
-        self.damping = 3 + (self.q >> 6)
-        B, H, W = batch, self.H, self.W
-        u8 = dict(dtype=torch.uint8, device=self.dev)
-        mk = lambda: (torch.zeros((B, H, W), **u8), torch.zeros((B, H // 2, W // 2), **u8),
-                      torch.zeros((B, H // 2, W // 2), **u8))
-        self.src, self.rec, self.fin = mk(), mk(), mk()
+        self.damping = int(CDEF_DAMPING[self.q])
+        self._ws = self._alloc(buffers(self.W, self.H, batch, 0, self.intra_in_inter)["work"])
+        self.src, self.rec, self.fin, self._dbk, self._cdf = (
+            tuple(self._ws[f"{s}_{c}"] for c in "yuv") for s in ("src", "rec", "fin", "dbk", "cdf"))
         self.pool = cf.ThreadPoolExecutor(max_workers=threads or min(32, os.cpu_count() or 8))
         self._gop_cap = 0
+        self._slots = []
+        self._keep = ()
         self.lock = None  # set by the worker's engine cache
         self.staging = None
         self._copy_stream = torch.cuda.Stream(self.dev)
         self._copy_pool = cf.ThreadPoolExecutor(max_workers=1)
 
-    def _lf_level(self, q: int | None = None) -> int:
-        return lf_level(self.q if q is None else q)
+    def _alloc(self, group: dict) -> dict:
+        return {n: self.torch.zeros(shape, dtype=getattr(self.torch, dt), device=self.dev)
+                for n, (shape, dt) in group.items()}
 
-    _NAMES = ("mode", "mv", "ly", "lu", "lv", "tabs", "fbidx", "sse", "lr")
+    @staticmethod
+    def estimate(width: int, height: int, batch: int, gop: int, intra_in_inter: bool = False) -> dict:
+        """{"dev": bytes} of an engine that has run a GOP of `gop` frames: the sum over
+        buffers() (workspace, two slots, one GOP's uploads); needs no GPU.  _collect's packing
+        buffers depend on the data (the nonzero levels of the GOP), live only during the copy
+        and are not counted."""
+        d = buffers(*av1m.coded_size(width, height), batch, gop, intra_in_inter)
+        return {"dev": _nbytes(d["work"]) + 2 * _nbytes(d["slot"]) + _nbytes(d["upload"])}
+
+    def footprint(self) -> dict:
+        """{"dev": bytes} of the device tensors the engine holds now (estimate()'s terms)."""
+        held = [*self._ws.values(), *(x for S in self._slots for x in S.values()), *self._keep]
+        return {"dev": sum(x.numel() * x.element_size() for x in held)}
 
     def _alloc_gop(self, F: int):
         """Two GOP decision buffers (slots): the GPU fills one while the previous GOP's is
         compacted and copied to the host on the copy stream (encode_gop(async_host=True))."""
-        torch = self.torch
         if F <= self._gop_cap:
             return
-        B, nb, nfb = self.B, self.nb, self.nfb
-        d = self.dev
-        self._slots = []
-        for _ in range(2):
-            self._slots.append({
-                "mode": torch.zeros((F, B, nb), dtype=torch.int32, device=d),
-                "mv": torch.zeros((F, B, nb), dtype=torch.int32, device=d),
-                "ly": torch.zeros((F, B, nb, 256), dtype=torch.int16, device=d),
-                "lu": torch.zeros((F, B, nb, 64), dtype=torch.int16, device=d),
-                "lv": torch.zeros((F, B, nb, 64), dtype=torch.int16, device=d),
-                "tabs": torch.zeros((F, B, 16), dtype=torch.uint8, device=d),
-                "fbidx": torch.zeros((F, B, nfb), dtype=torch.int8, device=d),
-                "sse": torch.zeros((F, B, 3), dtype=torch.int64, device=d),
-                "lr": torch.zeros((F, B, 3, self.nu, 3), dtype=torch.int32, device=d),
-                **({"ib": torch.zeros((F, B, nb), dtype=torch.uint8, device=d)} if self.intra_in_inter else {}),
-            })
+        slot = buffers(self.W, self.H, self.B, F, self.intra_in_inter)["slot"]
+        self._slots = [self._alloc(slot) for _ in range(2)]
         self._slot_busy = [None, None]
         self._slot = 0
         self._gop_cap = F
@@ -157,120 +204,65 @@ class Av1GpuEngine:
         if self._slot_busy[s] is not None:  # the previous GOP in this slot is still being collected
             self._slot_busy[s].result()
             self._slot_busy[s] = None
-        for n in self._NAMES + (("ib",) if self.intra_in_inter else ()):
-            setattr(self, "g_" + n, self._slots[s][n])
         return s
 
     # ------------------------------------------------------------------ one frame ----
-    def _frame(self, t: int, key: bool, nseg: int, qarr, lvl, q_rate):
+    def _frame(self, G: dict, t: int, key: bool, B: int, qarr, lvl, q_rate):
+        """Frame t of the first B segments into GOP slot G: launches on [:B] views of the
+        workspace (buffers() has the aliasing rules), no allocation."""
         from ..ops import av1 as ops
 
-        torch = self.torch
         lib = _gpu()
         st = stream(self.dev)
-        W, H, B, q = self.W, self.H, nseg, self.q
-        sy, su, sv = (x[:B] for x in self.src)
-        ry, ru, rv = (x[:B] for x in self.rec)
-        fy, fu, fv = (x[:B] for x in self.fin)
-        mode, mv = self.g_mode[t, :B], self.g_mv[t, :B]
-        ly, lu, lv = self.g_ly[t, :B], self.g_lu[t, :B], self.g_lv[t, :B]
+        W, H, w, h, dmp = self.W, self.H, self.w, self.h, self.damping
+        ws = {n: x[:B] for n, x in self._ws.items() if n != "memo"}
+        src, rec, fin, dbk, cdf = ([x[:B] for x in s] for s in (self.src, self.rec, self.fin, self._dbk, self._cdf))
+        mode, mv = G["mode"][t, :B], G["mv"][t, :B]
+        lev = [G[k][t, :B] for k in ("ly", "lu", "lv")]
         if key:
             if self.intra_in_inter:
-                self.g_ib[t, :B].zero_()
-            if self.cfl:
-                _ok(lib.tv_av1e_intra_tools(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly),
-                                            _p(lu), _p(lv), W, H, B, _p(qarr), av1m.TOOL_CFL, st))
-            else:
-                _ok(lib.tv_av1e_intra(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv), _p(ly),
-                                      _p(lu), _p(lv), W, H, B, _p(qarr), st))
+                G["ib"][t, :B].zero_()
+            _ok(lib.tv_av1e_intra(*map(_p, src), *map(_p, rec), _p(mode), _p(mv), *map(_p, lev), W, H, B, _p(qarr),
+                                  self.tools, st))
         else:
-            if getattr(self, "_mvtmp", None) is None:
-                self._mvtmp = torch.empty(self.B * self.nb, dtype=torch.int32, device=self.dev)
-                self._satd = torch.empty(self.B, dtype=torch.int64, device=self.dev)  # per-segment frame SATD
-                # refinement memo: 2 x [B][nb] x (11 MV words + 11 SATDs + a count)
-                self._memo = torch.empty(2 * self.B * self.nb * (11 * 8 + 1), dtype=torch.uint8, device=self.dev)
-            if not self.intra_in_inter:
-                _ok(lib.tv_av1e_inter(_p(sy), _p(su), _p(sv), _p(fy), _p(fu), _p(fv), _p(ry), _p(ru), _p(rv),
-                                      _p(mode), _p(mv), _p(self._mvtmp), _p(self._satd), _p(self._memo), _p(ly),
-                                      _p(lu), _p(lv), W, H, B, _p(qarr), st))
-            else:
-                if getattr(self, "_ibcost", None) is None:  # scratch of the intra-block passes, once per engine
-                    n = self.B * self.nb
-                    self._ibcost = torch.empty(n, dtype=torch.int32, device=self.dev)
-                    self._ibcand = torch.empty(n, dtype=torch.uint8, device=self.dev)
-                    self._ibcnt = torch.empty(self.B * 7, dtype=torch.int32, device=self.dev)
-                    self._iblist = torch.empty(7 * n, dtype=torch.int32, device=self.dev)
-                _ok(lib.tv_av1e_inter_cost(_p(sy), _p(su), _p(sv), _p(fy), _p(fu), _p(fv), _p(ry), _p(ru), _p(rv),
-                                           _p(mode), _p(mv), _p(self._mvtmp), _p(self._satd), _p(self._memo), _p(ly),
-                                           _p(lu), _p(lv), _p(self._ibcost), W, H, B, _p(qarr), st))
-                _ok(lib.tv_av1e_iblocks_tools(_p(sy), _p(su), _p(sv), _p(ry), _p(ru), _p(rv), _p(mode), _p(mv),
-                                              _p(ly), _p(lu), _p(lv), _p(self._ibcost), _p(self._ibcand),
-                                              _p(self.g_ib[t, :B]), _p(self._ibcnt), _p(self._iblist), W, H, B,
-                                              _p(qarr), av1m.TOOL_CFL if self.cfl else 0, st))
+            icost = ws["ibcost"] if self.intra_in_inter else None
+            _ok(lib.tv_av1e_inter(*map(_p, src), *map(_p, fin), *map(_p, rec), _p(mode), _p(mv), _p(ws["mvtmp"]),
+                                  _p(ws["satd"]), _p(self._ws["memo"]), *map(_p, lev),
+                                  None if icost is None else _p(icost), W, H, B, _p(qarr), st))
+            if self.intra_in_inter:
+                _ok(lib.tv_av1e_iblocks(*map(_p, src), *map(_p, rec), _p(mode), _p(mv), *map(_p, lev), _p(icost),
+                                        _p(ws["ibcand"]), _p(G["ib"][t, :B]), _p(ws["ibcnt"]), _p(ws["iblist"]), W, H,
+                                        B, _p(qarr), self.tools, st))
             _ok(lib.tv_av1e_merge(_p(mode), _p(mv), W, H, B, st))
-        iy = torch.empty((B, H // 4, W // 4), dtype=torch.int32, device=self.dev)
-        iu = torch.empty((B, H // 8, W // 8), dtype=torch.int32, device=self.dev)
-        iv = torch.empty_like(iu)
-        _ok(lib.tv_av1e_lfinfo(_p(mode), W, H, B, _p(lvl), _p(iy), _p(iu), _p(iv), st))
+        info = (ws["iy"], ws["iu"], ws["iv"])
+        _ok(lib.tv_av1e_lfinfo(_p(mode), W, H, B, _p(lvl), *map(_p, info), st))
         # every transform / block edge of the encoder's planes is on the 16 (luma) / 8
         # (chroma) grid: blocks are 16x16 or merged 32 / 64 with one TX per plane
-        dy = ops.deblock(ry, iy, False, 0, estep=16)
-        du = ops.deblock(ru, iu, True, 0, estep=8)
-        dv = ops.deblock(rv, iv, True, 0, estep=8)
-        dirs, var = ops.cdef_dirs(dy)
+        for c in range(3):
+            ops.deblock(rec[c], info[c], c > 0, 0, estep=8 if c else 16, out=dbk[c])
+        dirs, var = ops.cdef_dirs(dbk[0], out=(ws["dirs"], ws["var"]))
         _ok(lib.tv_av1e_cdef_skip(_p(mode), _p(dirs), W, H, B, st))  # skip blocks are not filtered
-        se_y = ops.cdef_search(sy, dy, dirs, var, False, self.damping, pmask=CDEF_MASK_Y, checker=True)
-        se_u = ops.cdef_search(su, du, dirs, var, True, self.damping, luma_w8=W // 8, pmask=CDEF_MASK_UV, checker=True)
-        se_v = ops.cdef_search(sv, dv, dirs, var, True, self.damping, luma_w8=W // 8, pmask=CDEF_MASK_UV, checker=True)
-        py = torch.empty((B, self.nfb), dtype=torch.int8, device=self.dev)
-        puv = torch.empty_like(py)
-        _ok(lib.tv_av1e_cdef_choose(_p(se_y), _p(se_u), _p(se_v), _p(mode), W, H, B, _p(self.g_tabs[t, :B]),
-                                    _p(self.g_fbidx[t, :B]), _p(py), _p(puv), st))
-        self.fin = (ops.cdef_apply(dy, dirs, var, py, False, self.damping),
-                    ops.cdef_apply(du, dirs, var, puv, True, self.damping, luma_w8=W // 8),
-                    ops.cdef_apply(dv, dirs, var, puv, True, self.damping, luma_w8=W // 8))
+        se = [ops.cdef_search(src[c], dbk[c], dirs, var, c > 0, dmp, luma_w8=W // 8,
+                              pmask=CDEF_MASK_UV if c else CDEF_MASK_Y, checker=True, out=ws["se_" + "yuv"[c]])
+              for c in range(3)]
+        py, puv = ws["py"], ws["puv"]
+        _ok(lib.tv_av1e_cdef_choose(*map(_p, se), _p(mode), W, H, B, _p(G["tabs"][t, :B]), _p(G["fbidx"][t, :B]),
+                                    _p(py), _p(puv), st))
+        flt = cdf if self.lr_enabled else fin  # the last filter of the frame writes the next reference
+        for c in range(3):
+            ops.cdef_apply(dbk[c], dirs, var, puv if c else py, c > 0, dmp, luma_w8=W // 8, out=flt[c])
         if self.lr_enabled:
-            self.fin = self._restore(t, B, q_rate, (dy, du, dv))
-        w, h = self.w, self.h
-        if B < self.B:  # keep full-batch planes: the slice's final frames become the reference
-            fin = [torch.empty_like(x) for x in self.src]
-            for full, part in zip(fin, self.fin):
-                full[:B].copy_(part)
-            self.fin = tuple(fin)
-        for c, (s, f) in enumerate(zip(self.src, self.fin)):
-            self.g_sse[t, :B, c] = self._unit_sse(s[:B], f[:B], w >> (c > 0), h >> (c > 0)).sum(dim=1)
-
-    def _unit_sse(self, a, b, vw: int | None = None, vh: int | None = None):
-        """(B, h, w) uint8 pair -> per-64x64-unit SSE (B, units) int64 (ceil layout) over
-        the valid region vw x vh (default: the whole plane); one fused kernel."""
-        torch = self.torch
-        B, h, w = a.shape
-        out = torch.empty((B, (-(-h // 64)) * (-(-w // 64))), dtype=torch.int64, device=self.dev)
-        _ok(_gpu().tv_av1e_unit_sse(_p(a), _p(b), w, h, w if vw is None else vw, h if vh is None else vh, B, _p(out),
-                                    stream(self.dev)))
-        return out
-
-    def _restore(self, t: int, B: int, rate, dbk):
-        """Normative self-guided restoration search + apply on the CDEF output (7.17 unit
-        grid and stripes; `dbk` = the deblocked pre-CDEF planes the stripe edges read): the
-        golden encoder's per-unit off / set-4 / set-10 choice (SSE + rate, first minimum), one
-        fused k_sgr_select launch per plane."""
-        from ..ops import av1 as ops
-
-        torch = self.torch
-        st = stream(self.dev)
-        rate = rate.to(torch.int64).contiguous()
-        out = []
-        for p, (S, X, D) in enumerate(zip((x[:B] for x in self.src), self.fin, dbk)):
-            h, w = X.shape[1], X.shape[2]
-            nu = lr_grid(w) * lr_grid(h)
-            prm = torch.empty((B, nu, 3), dtype=torch.int32, device=self.dev)
-            o = torch.empty_like(X)
-            ok(_gpu().tv_gpu_sgr_select(_p(S), _p(X), _p(D), w, h, 1 if p else 0, B, _p(rate), _p(prm), _p(o), st),
-               _gpu(), "tv_av1_gpu_last_error")
-            self.g_lr[t, :B, p, :nu] = prm
-            out.append(o)
-        return tuple(out)
+            # Normative self-guided restoration search + apply on the CDEF output (7.17 unit grid
+            # and stripes, whose edges read the deblocked planes): the golden encoder's per-unit
+            # off / set-4 / set-10 choice (SSE + rate, first minimum), one fused launch per plane
+            for c in range(3):
+                _, prm = ops.sgr_select(src[c], cdf[c], dbk[c], c > 0, q_rate, out=fin[c], prm=ws["prm_" + "yuv"[c]])
+                G["lr"][t, :B, c, :prm.shape[1]] = prm
+        for c in range(3):  # per-64x64-unit SSE over the display region, summed per segment
+            u = ws["sse_" + "yuv"[c]]
+            _ok(lib.tv_av1e_unit_sse(_p(src[c]), _p(fin[c]), W >> (c > 0), H >> (c > 0), w >> (c > 0), h >> (c > 0), B,
+                                     _p(u), st))
+            self.torch.sum(u, dim=1, out=G["sse"][t, :B, c])
 
     def encode_gop(self, nframes: int, load_frame, nseg: int | None = None, qmap=None, async_host: bool = False):
         """Run the GPU part of one GOP for all B segments.  load_frame(t, (Y, U, V)) fills
@@ -291,23 +283,23 @@ class Av1GpuEngine:
             qm = np.repeat(np.asarray(col, np.int32)[:, None], nseg, axis=1)
         else:
             qm = np.clip(np.asarray(qmap, np.int32).reshape(nframes, nseg), 1, 255)
-        lv = np.array([[[lf_level(int(x))] * 4 for x in row] for row in qm], np.int32)
+        lv = np.repeat(LF_LEVEL[qm][:, :, None], 4, axis=2)
         # pinned + non_blocking: a pageable upload would block the host on the previous
         # GOP's kernels (the stream drains before this GOP's first launch)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(self.dev, non_blocking=True)
         qd = up(qm)
         ld = up(lv)
-        rd = up(np.array([[lr_rate_cost(int(x)) for x in row] for row in qm], np.int64))
+        rd = up(LR_RATE[qm])
         self._keep = (qd, ld, rd)
+        S = self._slots[slot]
         if not self.lr_enabled:
-            self.g_lr[:nframes, :nseg, :, :, 0] = -1
+            S["lr"][:nframes, :nseg, :, :, 0] = -1
         for t in range(nframes):
             load_frame(t, self.src)
-            self._frame(t, t == 0, nseg, qd[t], ld[t], rd[t])
+            self._frame(S, t, t == 0, nseg, qd[t], ld[t], rd[t])
         self.nseg = nseg
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev))
-        S = self._slots[slot]
         if not async_host:
             return self._collect(S, ev, nframes, nseg, qm)
         fut = self._copy_pool.submit(self._collect, S, ev, nframes, nseg, qm)
@@ -364,7 +356,7 @@ class Av1GpuEngine:
         for t in range(g.nframes):
             tabs = g.tabs[t, b]
             q = int(g.qm[t, b])
-            fp = av1m.frame_params(g.key[t], q, [lf_level(q)] * 4, 0, self.damping, tabs[:8], tabs[8:])
+            fp = av1m.frame_params(g.key[t], q, [int(LF_LEVEL[q])] * 4, 0, self.damping, tabs[:8], tabs[8:])
             lev = [pk[0][pk[1][t, b]:] for pk in g.packed]  # eob-truncated scan-order TBs
             tus.append(wr.write(fp, np.ascontiguousarray(g.mode[t, b]), np.ascontiguousarray(g.mv[t, b]), lev[0],
                                 lev[1], lev[2], np.ascontiguousarray(g.fbidx[t, b]), packed=2, seq_header=g.key[t],

@@ -54,10 +54,26 @@ def n_units(w: int, h: int) -> int:
     return -(-w // RU) * -(-h // RU)
 
 
+def _out(out, shape, dtype, like, apart=()):
+    """The output tensor of a GPU op: a fresh one, or the caller's `out=` after a check of its
+    shape, dtype, device and contiguity (the kernels index it densely).  `apart`: inputs whose
+    neighbouring tiles the kernel reads; `out` must be none of them."""
+    import torch
+
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != like.device or not out.is_contiguous():
+        raise ValueError(f"out= must be a contiguous {dtype} tensor of shape {tuple(shape)} on {like.device}")
+    if any(out.data_ptr() == x.data_ptr() for x in apart):
+        raise ValueError("out= is an input of a kernel that reads neighbouring tiles")
+    return out
+
+
 # --------------------------------------------------------------------------- CDEF ----
-def cdef_dirs(Y):
+def cdef_dirs(Y, out=None):
     """Direction (0..7) and variance of every 8x8 block.  numpy (h, w) -> (dir, var) of
-    shape (h/8, w/8); torch (B, h, w) cuda -> tensors (B, h/8 * w/8)."""
+    shape (h/8, w/8); torch (B, h, w) cuda -> tensors (B, h/8 * w/8), written to the pair
+    `out` when given."""
     if _is_np(Y):
         h, w = Y.shape
         d = np.zeros((h // 8, w // 8), np.uint8)
@@ -68,18 +84,19 @@ def cdef_dirs(Y):
 
     B, h, w = Y.shape
     n8 = (h // 8) * (w // 8)
-    d = torch.empty((B, n8), dtype=torch.uint8, device=Y.device)
-    v = torch.empty((B, n8), dtype=torch.int32, device=Y.device)
+    d = _out(out and out[0], (B, n8), torch.uint8, Y)
+    v = _out(out and out[1], (B, n8), torch.int32, Y)
     _check(_gpu().tv_gpu_cdef_dirs(_t(Y.contiguous()), w, h, B, _t(d), _t(v), stream(Y.device)))
     return d, v
 
 
 def cdef_search(src, rec, dirs, var, chroma: bool, damping: int = 5, luma_w8: int | None = None,
-                pmask: int = (1 << 64) - 1, checker: bool = False):
+                pmask: int = (1 << 64) - 1, checker: bool = False, out=None):
     """SSE of every (64x64 filter block, preset) after CDEF: numpy -> (nfb, 64) uint64;
     torch (B, h, w) -> (B, nfb, 64) int64.  `pmask` (GPU path) restricts the evaluated
     presets (bit p); the others report 2^40.  `checker`: only the 8x8 (chroma 4x4) blocks
-    with (bx + by) even are measured (the AV1 encoder's search)."""
+    with (bx + by) even are measured (the AV1 encoder's search).  `out` (GPU path): the
+    tensor to write instead of a fresh one."""
     if _is_np(rec):
         h, w = rec.shape
         lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
@@ -91,15 +108,17 @@ def cdef_search(src, rec, dirs, var, chroma: bool, damping: int = 5, luma_w8: in
 
     B, h, w = rec.shape
     lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
-    out = torch.empty((B, n_fb(w, h, chroma), PRESETS), dtype=torch.int64, device=rec.device)
+    out = _out(out, (B, n_fb(w, h, chroma), PRESETS), torch.int64, rec)
     _check(_gpu().tv_gpu_cdef_search(_t(src.contiguous()), _t(rec.contiguous()), w, h, B, int(chroma),
                                      _t(dirs), _t(var), lw8, dirs.shape[-1], damping, _t(out), stream(rec.device),
                                      pmask, int(checker)))
     return out
 
 
-def cdef_apply(rec, dirs, var, fb_preset, chroma: bool, damping: int = 5, luma_w8: int | None = None):
-    """Filter with one preset index per filter block (-1 = off)."""
+def cdef_apply(rec, dirs, var, fb_preset, chroma: bool, damping: int = 5, luma_w8: int | None = None,
+               out=None):
+    """Filter with one preset index per filter block (-1 = off).  `out` (GPU path): the tensor
+    to write instead of a fresh one; the kernel reads neighbouring tiles, so never `rec`."""
     if _is_np(rec):
         h, w = rec.shape
         lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
@@ -112,7 +131,7 @@ def cdef_apply(rec, dirs, var, fb_preset, chroma: bool, damping: int = 5, luma_w
 
     B, h, w = rec.shape
     lw8 = luma_w8 or (w * (2 if chroma else 1)) // 8
-    out = torch.empty_like(rec)
+    out = _out(out, rec.shape, torch.uint8, rec, apart=(rec,))
     fbp = fb_preset.to(device=rec.device, dtype=torch.int8).contiguous()
     _check(_gpu().tv_gpu_cdef_apply(_t(rec.contiguous()), w, h, B, int(chroma), _t(dirs), _t(var), lw8,
                                     dirs.shape[-1], damping, _t(fbp), _t(out), stream(rec.device)))
@@ -224,6 +243,26 @@ def sgr_apply(rec, params):
         pr = torch.as_tensor(np.asarray(params, np.int32)).to(rec.device).reshape(B, -1, 3).contiguous()
     _check(_gpu().tv_gpu_sgr_apply(_t(rec.contiguous()), w, h, B, _t(pr), _t(out), stream(rec.device)))
     return out
+
+
+def sgr_select(src, cdef, dbk, chroma: bool, rate, out=None, prm=None):
+    """The encoder's restoration of a plane (GPU only; k_sgr_select): per 64-px unit the
+    choice between unrestored and every av1_enc.h lr_set() by SSE + rate, and the restored
+    plane.  src / cdef / dbk: (B, h, w) uint8 source, CDEF output and deblocked planes (the
+    stripe edges read `dbk`); rate: (B,) int64 rate of a restored unit per segment.  Returns
+    (restored plane, prm (B, units, 3) int32 = (set | -1, xqd0, xqd1)), written to `out` /
+    `prm` when given; the kernel reads neighbouring tiles, so `out` is none of the inputs."""
+    import torch
+
+    B, h, w = cdef.shape
+    nu = max(1, (w + 32) // 64) * max(1, (h + 32) // 64)  # av1_defs.h lr_count_units
+    out = _out(out, cdef.shape, torch.uint8, cdef, apart=(cdef, dbk))
+    prm = _out(prm, (B, nu, 3), torch.int32, cdef)
+    if rate.dtype != torch.int64 or rate.numel() != B or not rate.is_contiguous():
+        raise ValueError("rate must be a contiguous int64 tensor of one entry per segment")
+    _check(_gpu().tv_gpu_sgr_select(_t(src.contiguous()), _t(cdef.contiguous()), _t(dbk.contiguous()), w, h,
+                                    int(chroma), B, _t(rate), _t(prm), _t(out), stream(cdef.device)))
+    return out, prm
 
 
 def _solve_sgr(st: np.ndarray) -> np.ndarray:
@@ -379,11 +418,13 @@ def random_lf_info(w: int, h: int, rng: np.random.Generator, chroma: bool = Fals
     return lf_info(f["txw"], f["txh"], f["bw"], f["bh"], f["lv"], f["lh"], f["sk"])
 
 
-def deblock(rec, info, chroma: bool = False, sharpness: int = 0, estep: int = 4):
+def deblock(rec, info, chroma: bool = False, sharpness: int = 0, estep: int = 4, out=None):
     """AV1 deblocking loop filter (7.14) of a plane: numpy (h, w) + info (h/4, w/4) -> the
     C++ golden model; torch (B, h, w) cuda + info (B, h/4, w/4) -> one fused HIP launch
     (k_deblock, both passes per 64x64 LDS tile).  estep (GPU): edge grid in samples, 8 / 16
-    only when every transform and block edge lies on it (the AV1 encoder's planes)."""
+    only when every transform and block edge lies on it (the AV1 encoder's planes).  `out`
+    (GPU): the tensor to write instead of a fresh one; the kernel reads neighbouring tiles, so
+    never `rec`."""
     if _is_np(rec):
         h, w = rec.shape
         out = np.empty_like(rec)
@@ -397,7 +438,7 @@ def deblock(rec, info, chroma: bool = False, sharpness: int = 0, estep: int = 4)
     if _is_np(info):
         info = torch.from_numpy(np.ascontiguousarray(info, np.uint32).view(np.int32))
     inf = info.to(device=rec.device, dtype=torch.int32).reshape(B, h // 4, w // 4).contiguous()
-    out = torch.empty_like(rec)
+    out = _out(out, rec.shape, torch.uint8, rec, apart=(rec,))
     _check(_gpu().tv_gpu_av1_deblock_step(_t(rec.contiguous()), _t(out), w, h, B, int(chroma), _t(inf), sharpness,
                                           estep, stream(rec.device)))
     return out

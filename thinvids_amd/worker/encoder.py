@@ -158,18 +158,12 @@ def _staging_bytes(spec: "EncodeSpec", batch: int) -> int:
 def engine_bytes(spec: "EncodeSpec", batch: int) -> int:
     """Device bytes of an engine for `spec` at `batch` segments, including the staging
     buffer the cache attaches to it (batch x GOP coded frames).  HEVC: the native
-    constructor's own size formulas (gpu_engine.estimate_footprint); AV1: its per-segment
-    GOP decision slots and frame sets (models/av1_engine.py allocations)."""
+    constructor's own size formulas (gpu_engine.estimate_footprint); AV1: the sum over the
+    engine's buffer declaration (Av1GpuEngine.estimate)."""
     if spec.codec == "av1":
-        from ..models.av1 import coded_size
+        from ..models.av1_engine import Av1GpuEngine
 
-        W, H = coded_size(spec.width, spec.height)
-        # two GOP decision slots of (mode, mv, 256 + 2 x 64 int16 levels) per 16x16 block
-        # and frame (~384 B per pixel of a GOP-64 segment), plus the source / recon /
-        # filtered frame sets and the filters' scratch (~11 coded frames)
-        eng = batch * (2 * spec.gop * (W // 16) * (H // 16) * 776 + 11 * W * H * 3 // 2)
-        if spec.intra_in_inter:  # candidate / accepted map per slot and frame, cost / flag / pass-list scratch
-            eng += batch * (W // 16) * (H // 16) * (2 * spec.gop + 33)
+        eng = Av1GpuEngine.estimate(spec.width, spec.height, batch, spec.gop, spec.intra_in_inter)["dev"]
     else:
         from ..models.gpu_engine import estimate_footprint
 
@@ -247,7 +241,8 @@ class EngineCache:
             eng = self._build(spec, batch)
             eng.lock = threading.Lock()
             eng.staging = None
-            fp = eng.footprint()["dev"] if hasattr(eng, "footprint") else None
+            # the AV1 engine allocates its GOP slots with the first GOP: its estimate is the charge
+            fp = eng.footprint()["dev"] if hasattr(eng, "footprint") and spec.codec != "av1" else None
             self._bytes[key] = (fp + _staging_bytes(spec, batch)) if fp is not None else need
             self._engines[key] = eng
             self._order.append(key)
