@@ -152,6 +152,34 @@ void tv_synth_frame_tiled(uint32_t seed, int t, int W, int H, int tile_w, int ti
 // tv::satd8x8 (tv/me_model.h) of one 8x8 block of differences, for the tests
 int tv_satd8x8(const int* d, int stride) { return satd8x8(d, stride); }
 
+// The golden SAO of one W x H picture (multiples of kCtb): tv::sao_decide_picture of the
+// deblocked planes dy, du, dv against the source at slice QP qp -> 3 packed words per CTB in
+// params, then tv::sao_picture -> oy, ou, ov.
+int tv_sao_picture_cpu(int W, int H, int qp, const uint8_t* sy, const uint8_t* su, const uint8_t* sv,
+                       const uint8_t* dy, const uint8_t* du, const uint8_t* dv, uint32_t* params, uint8_t* oy,
+                       uint8_t* ou, uint8_t* ov) {
+  if (W <= 0 || H <= 0 || W % kCtb || H % kCtb || qp < 0 || qp > 51) {
+    g_err = "tv_sao_picture_cpu: bad geometry or QP";
+    return -1;
+  }
+  return guard([&] {
+    Picture src, deb;
+    src.alloc(W, H);
+    deb.alloc(W, H);
+    const uint8_t* s[3] = {sy, su, sv};
+    const uint8_t* d[3] = {dy, du, dv};
+    uint8_t* o[3] = {oy, ou, ov};
+    for (int c = 0; c < 3; ++c) {
+      const size_t n = (size_t)src.pw(c) * src.ph(c);
+      std::memcpy(src.plane(c), s[c], n);
+      std::memcpy(deb.plane(c), d[c], n);
+    }
+    sao_decide_picture(src, deb, qp, params);
+    sao_picture(deb, params);
+    for (int c = 0; c < 3; ++c) std::memcpy(o[c], deb.plane(c), (size_t)deb.pw(c) * deb.ph(c));
+  });
+}
+
 // ------------------------------------ CPU encoder ---------------------------------------
 void* tv_cpu_encoder_new(int width, int height, int qp, int deblock, int range, int max_merge) {
   SeqConfig cfg;

@@ -572,32 +572,40 @@ void launch_phase_planes(FrameSet ref, uint8_t* phase, const Geo& g, int B, hipS
   k_phase_planes<<<grid, 256, 0, s>>>(ref, phase, g);
 }
 // ---------------------------------------- SAO ------------------------------------------
-// One block per CTB: statistics -> integer RD decision -> the SAO'd CTB, in one launch.  The
-// deblocked CTB of every component plus a one-sample border is staged in LDS (-1 marks
-// samples outside the picture; every global load of the stage is issued before the first
+// One workgroup per strip of kSaoStrip horizontally adjacent CTBs, one wave per CTB:
+// statistics -> integer RD decision -> the SAO'd CTB, in one launch.  The deblocked strip of
+// every component plus a one-sample ring is staged once in LDS as int16 pairs (-1 marks
+// samples outside the picture; every global load of a wave's rows is issued before its first
 // store), so the EO neighbour reads of both the statistics and the filter never touch global
-// memory, and the filtered CTB is written straight from the tile (no separate apply pass
-// re-reading the deblocked frame).  Statistics without LDS-atomic storms:
-//   * EO: each thread accumulates its samples' 4 classes x 4 categories (count, sum) in
-//     registers; one DPP wave reduction per counter, one LDS add per wave;
-//   * band: per wave, loop over the distinct bands present (ballot + readlane): one wave
-//     reduction and one LDS add per distinct band.
-// Then the shared integer RD decision (tv::sao_item / sao_window / sao_finish_pos: identical
-// to the CPU golden model), the band-position argmin of the 3 components on 3 waves.
-constexpr int kSaoT = 34;   // luma tile side with border
-constexpr int kSaoTc = 18;  // chroma
-// Tile rows are stored with pitch T + 2 and one column of offset, so a sample pair (even x,
-// x + 1) of the CTB is one aligned dword: the packed statistics read pairs as ds_read_b32.
-constexpr int kSaoP = kSaoT + 2, kSaoPc = kSaoTc + 2;
-constexpr int kSaoTile = kSaoT * kSaoP + 2 * kSaoTc * kSaoPc;
-constexpr int kSaoStage = (kSaoTile + 255) / 256;
-// tile index of (row, col) of component c (row / col 0 = the one-sample border)
-__device__ __forceinline__ int sao_tix(int c, int row, int col) {
-  return c == 0 ? row * kSaoP + col + 1 : kSaoT * kSaoP + (c - 1) * kSaoTc * kSaoPc + row * kSaoPc + col + 1;
-}
+// memory, and the filtered CTB is written straight from the tile.  After the staging barrier
+// a wave works alone on its CTB, all three components:
+//   * statistics: a lane keeps one pair column and walks down consecutive rows (luma 16 pair
+//     columns x 4 groups of 8 rows; chroma Cb | Cr on the 32-lane halves, 8 pair columns x 4
+//     groups of 4 rows), each tile row read once, the vertical sign of a row reused negated
+//     by the next; 4 classes x 4 packed 16-bit accumulators per component;
+//   * one transpose-reduce per component leaves every counter on the lanes that run
+//     tv::sao_best_offset for it; class sums, the luma argmin and the joint Cb + Cr argmin
+//     (the order of tv::sao_finish_pos) with DPP row sums and scalar compares;
+//   * the filter takes the parameters from SGPRs, a straight-line body per EO class.
+// Waves of a partial strip whose CTB lies beyond the picture only stage and meet the barriers.
+// The display-area squared error is summed per wave, combined in LDS, one global atomic per
+// component and strip.
+constexpr int kSaoStrip = 4;                    // CTBs (= waves) per workgroup
+constexpr int kSaoRows = 34, kSaoRowsC = 18;    // tile rows with the ring
+// Tile rows in dwords (one int16 pair each): sample x of the strip sits at int16 index x + 2,
+// so a pair (even x, x + 1) is one aligned dword and the ring columns -1 / 32 S are the odd /
+// even half of the first / last dword.  Pitch % 32 = 2: the row groups of a 32-lane half land
+// on disjoint banks (luma 16 rg + p, chroma 8 rg + p).
+constexpr int kSaoPd = 16 * kSaoStrip + 2, kSaoPdC = 8 * kSaoStrip + 2;
+constexpr int kSaoLumaDw = kSaoRows * kSaoPd, kSaoChromaDw = kSaoRowsC * kSaoPdC;
+constexpr int kSaoTileDw = kSaoLumaDw + 2 * kSaoChromaDw;
+constexpr int kSaoSrcDw = 8 * kSaoStrip + 2, kSaoSrcDwC = 4 * kSaoStrip + 2;  // plane dwords per tile row
+static_assert(kSaoSrcDw <= 64 && kSaoSrcDwC <= 32, "a tile row is staged by one wave (chroma: one half per plane)");
+static_assert(8 * (kSaoTileDw * 4 + 64) <= 160 * 1024, "8 workgroups per CU");
 typedef short sao_s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ sao_s2 sao_pair(uint32_t w) { return __builtin_bit_cast(sao_s2, w); }
 typedef unsigned short sao_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ sao_u2 sao_upair(sao_s2 w) { return __builtin_bit_cast(sao_u2, w); }
 // per half: -1, 0, 1 for |d| < 2^15 -- shifts and an OR (v_pk_ashrrev / v_pk_lshrrev), no
 // compares: (d >> 15) is -1 for d < 0, ((-d) >>> 15) is 1 for d > 0
 __device__ __forceinline__ sao_s2 sao_sign2(sao_s2 d) {
@@ -618,361 +626,408 @@ __device__ __forceinline__ sao_s2 sao_pkmin(sao_s2 a, sao_s2 b) {
   asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(__builtin_bit_cast(uint32_t, a)), "v"(__builtin_bit_cast(uint32_t, b)));
   return sao_pair(r);
 }
-
-__device__ __forceinline__ void sao_tile_pos(int i, int& c, int& j) {
-  c = i < kSaoT * kSaoT ? 0 : (i < kSaoT * kSaoT + kSaoTc * kSaoTc ? 1 : 2);
-  j = c == 0 ? i : i - kSaoT * kSaoT - (c - 1) * kSaoTc * kSaoTc;
+__device__ __forceinline__ sao_s2 sao_clamp1(sao_s2 d) {  // per half: sign of d
+  return sao_pkmin(sao_pkmax(d, sao_s2{-1, -1}), sao_s2{1, 1});
 }
 
-__global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, FrameSet out, uint32_t* sao, Geo g,
-                                                    const int8_t* qp, const RcTables* rc,
-                                                    unsigned long long* sse) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  int ctu, b;
-  xcd_ctb(ctu, b);
-  const long long lam16 = rc->sao_lam16[qp[b]];
-  const int cx = ctu % g.wc, cy = ctu / g.wc;
-  __shared__ SaoStats st[3];
-  __shared__ __align__(16) int16_t tile[kSaoTile];  // luma 34 x 34, then Cb, Cr 18 x 18 (sao_tix)
-  __shared__ int bpos[3];
-  // band statistics: a packed (sum * 2048 + count) histogram per component with 16 copies
-  // (lane & 15), so same-band lanes of a wave rarely hit one LDS address
-  __shared__ int bh[3][32][16];
-  for (int i = tid; i < 3 * (int)(sizeof(SaoStats) / 4); i += 256) reinterpret_cast<int*>(st)[i] = 0;
-  if (kSaoBandOffsets)
-    for (int i = tid; i < 3 * 32 * 16; i += 256) (&bh[0][0][0])[i] = 0;
-  {  // deblocked CTB + 1-sample ring as aligned dwords (a CTB edge is a multiple of 4, so a
-     // dword is wholly inside or wholly outside the plane): luma 34 rows x 10 dwords (items
-     // tid, tid + 256), chroma 2 x 18 rows x 6 dwords (item tid); each slot has one component,
-     // so the row / dword split is a division by a constant.  Every load is issued before the
-     // first LDS store.  The 4 bytes land as two int16 pairs (v_perm), each one aligned
-     // dword store: dword d of a row covers tile columns 4d - 3 .. 4d, so pair 0 is stored
-     // for d >= 1 and pair 1 for d < last (column -1 / T are the pitch padding, never read).
-    uint32_t* tile32 = reinterpret_cast<uint32_t*>(tile);
-    uint32_t v[3];
-    int at[3], dw[3], nd[3];
-    bool act[3], in[3];
+// EO statistics of ROWS consecutive rows of one pair column.  t: the pair's dword in the tile
+// row above the first (tile pitch PD dwords); sp[r]: the two source bytes of row r.  Row r's
+// pair and its neighbours one sample to the left / right come from three dwords; the rows
+// move down a register window, so every tile row is read once.  Classes (sao_eo_dir): 0
+// horizontal, 1 vertical, 2 135 degrees, 3 45 degrees; e = sign(v - a) + sign(v - b) per half.
+// The vertical sign against the row below is the next row's sign against the row above,
+// negated.  MASK (CTBs on the picture border): e = 0 where a class neighbour is outside (-1).
+// Per class four accumulators of w = 16 (orig - v) + 1 per half, in wrapping 16-bit
+// arithmetic: w [e = -2], w |e| over e < 0, w e over e > 0, w [e = 2]; sao_counters takes
+// the categories e = -1 / e = 1 out of the middle two.
+template <bool MASK, int ROWS, int PD>
+__device__ __forceinline__ void sao_walk(const uint32_t* t, const uint32_t (&sp)[ROWS], sao_u2 (&acc)[4][4]) {
+  sao_s2 L0, C0, R0, L1, C1, R1, L2, C2, R2;
+  auto row = [&](int r, sao_s2& L, sao_s2& C, sao_s2& R) {
+    const uint32_t Pv = t[r * PD - 1], Cv = t[r * PD], Nv = t[r * PD + 1];
+    L = sao_pair(__builtin_amdgcn_alignbyte(Cv, Pv, 2));  // samples (x - 1, x)
+    R = sao_pair(__builtin_amdgcn_alignbyte(Nv, Cv, 2));  // samples (x + 1, x + 2)
+    C = sao_pair(Cv);
+  };
+  row(0, L0, C0, R0);
+  row(1, L1, C1, R1);
+  const sao_s2 zero = {0, 0}, one = {1, 1}, sixteen = {16, 16};
+  const sao_u2 uone = {1, 1};
+  sao_s2 pdn = sao_clamp1(C0 - C1);  // sign(row above - row): what the row above saw downwards
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      int c, row, d;
-      if (k < 2) {
-        const int i = tid + 256 * k;
-        c = 0;
-        row = i / 10;
-        d = i - 10 * row;
-        act[k] = i < 34 * 10;
-      } else {
-        const int pl = tid >= 108 ? 1 : 0, j = tid - 108 * pl;
-        c = 1 + pl;
-        row = j / 6;
-        d = j - 6 * row;
-        act[k] = tid < 2 * 108;
-      }
-      const int n = c ? 16 : 32, w = c ? g.W / 2 : g.W, h = c ? g.H / 2 : g.H;
-      const int x = cx * n - 4 + 4 * d, y = cy * n - 1 + row;
-      in[k] = act[k] && x >= 0 && x < w && y >= 0 && y < h;
-      v[k] = in[k] ? *reinterpret_cast<const uint32_t*>(deb.plane(c, b, g) + (long)y * w + x) : 0u;
-      at[k] = (sao_tix(c, row, -1) >> 1) + 2 * d - 1;  // dword of tile columns 4d - 3, 4d - 2
-      dw[k] = d;
-      nd[k] = c ? 6 : 10;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (!act[k]) continue;
-      const uint32_t lo = in[k] ? __builtin_amdgcn_perm(0u, v[k], 0x0c010c00u) : 0xFFFFFFFFu;  // outside: -1 pairs
-      const uint32_t hi = in[k] ? __builtin_amdgcn_perm(0u, v[k], 0x0c030c02u) : 0xFFFFFFFFu;
-      if (dw[k] >= 1) tile32[at[k]] = lo;
-      if (dw[k] < nd[k] - 1) tile32[at[k] + 1] = hi;
-    }
-  }
-  // one region per wave: waves 0/1 = luma rows 0-15 / 16-31, wave 2 = Cb, wave 3 = Cr.
-  // Counts and sums travel packed as sum * 2048 + count (count <= 1024, |sum| <= 255 * 1024):
-  // one wave reduction per EO counter, not two.
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar component logic
-  const int c = wave < 2 ? 0 : wave - 1;
-  const int n = c ? 16 : 32, w = c ? g.W / 2 : g.W;
-  const int nsh = c ? 4 : 5;  // log2 n: the sample index splits with shifts, not a runtime division
-  const int iters = c ? 4 : 8;
-  const uint8_t* S = src.plane(c, b, g) + (long)(cy * n) * w + cx * n;
-  // A CTB away from the picture edge has no outside (-1) neighbours: its statistics run on
-  // sample PAIRS in packed 16-bit arithmetic (v_pk_*: two samples per instruction, the 9
-  // neighbour dwords of a pair read once for all 4 classes).  Edge CTBs take the per-sample
-  // path with the validity checks.  Both give the same counters.
-  static_assert(!kSaoBandOffsets, "the packed statistics carry no band histogram");
-  const bool interior = cx > 0 && cy > 0 && cx < g.wc - 1 && cy < g.hc - 1;
-  const int piters = c ? 2 : 4;  // pairs per lane: luma 16 rows x 16 pairs, chroma 16 x 8
-  int sv[8] = {};
-  uint32_t sp[4] = {};
-  if (interior) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {  // source pairs of this lane, loads in flight together
-      const int pidx = lane + 64 * k;
-      const int ly = (c == 0 ? wave * 16 : 0) + (pidx >> (nsh - 1)), lx = 2 * (pidx & ((n >> 1) - 1));
-      sp[k] = k < piters ? *reinterpret_cast<const uint16_t*>(S + ly * w + lx) : 0u;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {  // source samples of this lane, loads in flight together
-      const int i = (c == 0 ? wave * 512 : 0) + lane + 64 * k;
-      sv[k] = k < iters ? S[(i >> nsh) * w + (i & (n - 1))] : 0;
-    }
-  }
-  __syncthreads();
-  int eo[4][4];
-  if (interior) {
-    const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-    // per half and (class, category): sum(orig - deb) * 16 + count, one v_pk_mad per bin
-    // (count <= 4 samples per half, |sum| <= 4 * 255: |acc| < 2^14)
-    sao_s2 acc[4][4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[d][q] = sao_s2{0, 0};
-    const sao_s2 zero = {0, 0}, one = {1, 1}, mone = {-1, -1}, sixteen = {16, 16};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k >= piters) break;
-      const int pidx = lane + 64 * k;
-      const int ly = (c == 0 ? wave * 16 : 0) + (pidx >> (nsh - 1)), lx = 2 * (pidx & ((n >> 1) - 1));
-      uint32_t Pv[3], Cv[3], Nv[3];  // rows ly - 1, ly, ly + 1: dwords at lx - 2, lx, lx + 2
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const int i0 = sao_tix(c, ly + r, lx + 1) >> 1;  // tile column lx + 1 = sample lx (even index)
-        Pv[r] = tile32[i0 - 1];
-        Cv[r] = tile32[i0];
-        Nv[r] = tile32[i0 + 1];
-      }
-      sao_s2 L[3], R[3], Cc[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        L[r] = sao_pair(__builtin_amdgcn_alignbyte(Cv[r], Pv[r], 2));  // samples (lx - 1, lx)
-        R[r] = sao_pair(__builtin_amdgcn_alignbyte(Nv[r], Cv[r], 2));  // samples (lx + 1, lx + 2)
-        Cc[r] = sao_pair(Cv[r]);
-      }
-      const sao_s2 v = Cc[1];
-      const uint32_t o = sp[k];
-      const sao_s2 orig = {(short)(o & 255), (short)(o >> 8)};
-      const sao_s2 w = (orig - v) * sixteen + one;
-      // classes (sao_eo_dir): 0 horizontal, 1 vertical, 2 135 degrees, 3 45 degrees
-      const sao_s2 A[4] = {L[1], Cc[0], L[0], R[0]}, Bn[4] = {R[1], Cc[2], R[2], L[2]};
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const sao_s2 e = sao_pkmin(sao_pkmax(v - A[d], mone), one) + sao_pkmin(sao_pkmax(v - Bn[d], mone), one);
-        const sao_s2 pos = sao_pkmax(e, zero), neg = sao_pkmax(zero - e, zero);
-        const sao_s2 is[4] = {neg >> one, neg & one, pos & one, pos >> one};  // categories 1..4
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[d][q] += w * is[q];
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {  // both halves: F = 16 * sum + count (count <= 8)
-        const int F = __builtin_amdgcn_sdot2(acc[d][q], one, 0, false), C = F & 15;
-        eo[d][q] = (F - C) * 128 + C;  // sum * 2048 + count
-      }
-  } else {
-    // EO statistics per lane in one 64-bit register per class: four signed 16-bit fields
-    // (category 1..4) of sum(orig - deb) * 16 + count over the lane's <= 8 samples (|field| <=
-    // 255 * 8 * 16 + 8 < 2^15), added as one shifted 64-bit value per (sample, class) instead
-    // of four compare/select/adds; unpacked into the wave-sum format afterwards.
-    unsigned long long eo64[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (k >= iters) break;
-      const int i = (c == 0 ? wave * 512 : 0) + lane + 64 * k;
-      const int lx = i & (n - 1), ly = i >> nsh;
-      const int v = tile[sao_tix(c, ly + 1, lx + 1)];
-      const int d16 = (sv[k] - v) * 16 + 1;
-      const unsigned long long p64 = (unsigned long long)(long long)d16;
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        int dx, dy;
-        sao_eo_dir(d, dx, dy);
-        const int a = tile[sao_tix(c, ly + 1 + dy, lx + 1 + dx)], bb = tile[sao_tix(c, ly + 1 - dy, lx + 1 - dx)];
-        const int e = tv_min(tv_max(v - a, -1), 1) + tv_min(tv_max(v - bb, -1), 1);  // -2..2, 0 = none
-        const int f = e + 2 - (e > 0);  // category 1..4 -> field 0..3 (e = 0 is masked below)
-        eo64[d] += (a >= 0 && bb >= 0 && e != 0) ? p64 << (16 * f) : 0ull;
-      }
-      if (kSaoBandOffsets) atomicAdd(&bh[c][v >> 3][lane & 15], (sv[k] - v) * 2048 + 1);  // band statistics
+  for (int r = 0; r < ROWS; ++r) {
+    row(r + 2, L2, C2, R2);
+    const sao_s2 v = C1;
+    const sao_s2 orig = sao_pair(__builtin_amdgcn_perm(0u, sp[r], 0x0c010c00u));
+    const sao_u2 w = sao_upair((orig - v) * sixteen + one);
+    const sao_s2 dn = sao_clamp1(v - C2);
+    sao_s2 e[4] = {sao_clamp1(v - L1) + sao_clamp1(v - R1), dn - pdn, sao_clamp1(v - L0) + sao_clamp1(v - R2),
+                   sao_clamp1(v - R0) + sao_clamp1(v - L2)};
+    pdn = dn;
+    if (MASK) {  // samples are >= -1: min(a, b, 0) + 1 is 0 where a neighbour is outside, else 1
+      e[0] *= sao_pkmin(sao_pkmin(L1, R1), zero) + one;
+      e[1] *= sao_pkmin(sao_pkmin(C0, C2), zero) + one;
+      e[2] *= sao_pkmin(sao_pkmin(L0, R2), zero) + one;
+      e[3] *= sao_pkmin(sao_pkmin(R0, L2), zero) + one;
     }
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-      unsigned long long acc = eo64[d];
+      const sao_s2 pos = sao_pkmax(e[d], zero), neg = pos - e[d];
+      const sao_u2 up = sao_upair(pos), un = sao_upair(neg);
+      acc[d][0] += w * (un >> uone);
+      acc[d][1] += w * un;
+      acc[d][2] += w * up;
+      acc[d][3] += w * (up >> uone);
+    }
+    L0 = L1, C0 = C1, R0 = R1;
+    L1 = L2, C1 = C2, R1 = R2;
+  }
+}
+// The lane's 16 counters (class d, category q + 1 at 4 d + q) as sum * 2048 + count, the
+// format of the wave reduction.  Per half an accumulator is 16 sum + count with count <= 8
+// (its low 4 bits, |16 sum + count| < 2^15): sum * 2048 + count = 128 (16 sum + count) - 127 count.
+__device__ __forceinline__ void sao_counters(const sao_u2 (&acc)[4][4], int (&t)[16]) {
+  const sao_u2 two = {2, 2};
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int fv = (int)(int16_t)(acc & 0xffffu);  // 16 * sum + count
-        acc = (acc - (unsigned long long)(long long)fv) >> 16;
-        const int cnt = fv & 15;
-        eo[d][q] = ((fv - cnt) >> 4) * 2048 + cnt;  // sum * 2048 + count, as before
-      }
+  for (int d = 0; d < 4; ++d) {
+    const sao_u2 x[4] = {acc[d][0], acc[d][1] - two * acc[d][0], acc[d][2] - two * acc[d][3], acc[d][3]};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t xv = __builtin_bit_cast(uint32_t, x[q]);
+      const int cn = __builtin_amdgcn_sdot2(sao_pair(xv & 0x000F000Fu), sao_s2{-127, -127}, 0, false);
+      t[4 * d + q] = __builtin_amdgcn_sdot2(sao_pair(xv), sao_s2{128, 128}, cn, false);
     }
   }
-  {  // the 16 counters of the wave in one transpose-reduce: each exchange step (lanes 32,
-     // 16, 8, 4 apart) halves the values a lane holds -- it keeps one half and adds the
-     // partner's copy of it -- so lane L ends with counter (L >> 2) summed over 16 lanes; two
-     // quad DPP adds finish the sum (~40 VALU instead of 16 full wave reductions).  Lanes 32
-     // / 16 apart swap with v_permlane32_swap / v_permlane16_swap (gfx950), lanes 8 apart
-     // with a DPP row rotate; the halves are chosen with xor masks, not selects (a select
-     // of two array elements became a dynamically indexed array)
-    int t[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t[k] = eo[k >> 2][k & 3];
+}
+// The 16 counters of the wave in one transpose-reduce: each exchange step (lanes 32, 16, 8,
+// 4 apart) halves the values a lane holds -- it keeps one half and adds the partner's copy
+// of it -- and DPP quad adds finish the sum.  Lanes 32 / 16 apart swap with
+// v_permlane32_swap / v_permlane16_swap (gfx950), lanes 8 apart with a DPP row rotate; the
+// halves are chosen with xor masks, not selects (a select of two array elements became a
+// dynamically indexed array).  Whole wave: lane L ends with counter L >> 2.  HALF: the two
+// 32-lane halves are reduced apart (Cb | Cr, one more step 2 lanes apart): lane L ends with
+// counter (L & 31) >> 1 of its half.  Full wave only (no DPP in a divergent branch).
+template <bool HALF>
+__device__ __forceinline__ int sao_reduce16(int (&t)[16], int lane) {
+  if (!HALF) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {  // lanes 0-31 keep t[j], lanes 32-63 t[j + 8]
       const auto r = __builtin_amdgcn_permlane32_swap((unsigned)t[j], (unsigned)t[j + 8], false, false);
       t[j] = (int)(r[0] + r[1]);
     }
+  }
+  constexpr int n16 = HALF ? 8 : 4, n8 = n16 / 2, n4 = n8 / 2;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {  // even 16-lane rows keep t[j], odd rows t[j + 4]
-      const auto r = __builtin_amdgcn_permlane16_swap((unsigned)t[j], (unsigned)t[j + 4], false, false);
-      t[j] = (int)(r[0] + r[1]);
-    }
-    const int m8 = -((lane >> 3) & 1), m4 = -((lane >> 2) & 1);
+  for (int j = 0; j < n16; ++j) {  // even 16-lane rows keep t[j], odd rows t[j + n16]
+    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)t[j], (unsigned)t[j + n16], false, false);
+    t[j] = (int)(r[0] + r[1]);
+  }
+  const int m8 = -((lane >> 3) & 1), m4 = -((lane >> 2) & 1), m2 = -((lane >> 1) & 1);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int x = (t[j] ^ t[j + 2]) & m8;
-      t[j] = (t[j] ^ x) + dpp::mov<dpp::kRowRor8>(t[j + 2] ^ x);
-    }
-    {
-      const int x = (t[0] ^ t[1]) & m4;
-      t[0] = (t[0] ^ x) + __shfl_xor(t[1] ^ x, 4, 64);
-    }
-    int tot = t[0];
-    tot += dpp::mov<dpp::kQuadXor1>(tot);
+  for (int j = 0; j < n8; ++j) {
+    const int x = (t[j] ^ t[j + n8]) & m8;
+    t[j] = (t[j] ^ x) + dpp::mov<dpp::kRowRor8>(t[j + n8] ^ x);
+  }
+#pragma unroll
+  for (int j = 0; j < n4; ++j) {
+    const int x = (t[j] ^ t[j + n4]) & m4;
+    t[j] = (t[j] ^ x) + __shfl_xor(t[j + n4] ^ x, 4, 64);
+  }
+  int tot;
+  if (HALF) {
+    const int x = (t[0] ^ t[1]) & m2;
+    tot = (t[0] ^ x) + dpp::mov<dpp::kQuadXor2>(t[1] ^ x);
+  } else {
+    tot = t[0];
     tot += dpp::mov<dpp::kQuadXor2>(tot);
-    const int k = lane >> 2;  // class k >> 2, category (k & 3) + 1
-    if ((lane & 3) == 0 && (tot & 2047)) {
-      atomicAdd(&st[c].eo_n[k >> 2][(k & 3) + 1], tot & 2047);
-      atomicAdd(&st[c].eo_s[k >> 2][(k & 3) + 1], (tot - (tot & 2047)) / 2048);
-    }
   }
-  __shared__ SaoTables tab;
-  __shared__ uint32_t prm[3];
-  __syncthreads();
-  if (kSaoBandOffsets && tid < 96) {  // fold the histogram copies into the band counters
-    const int cc = tid >> 5, band = tid & 31;
-    int tot = 0;
+  tot += dpp::mov<dpp::kQuadXor1>(tot);
+  return tot;
+}
+template <int CTRL>
+__device__ __forceinline__ long long sao_dpp_add64(long long v) {
+  const unsigned lo = (unsigned)dpp::mov<CTRL>((int)v), hi = (unsigned)dpp::mov<CTRL>((int)(v >> 32));
+  return v + (long long)((unsigned long long)hi << 32 | lo);
+}
+__device__ __forceinline__ long long sao_readlane64(long long v, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l);
+  return (long long)((unsigned long long)hi << 32 | lo);
+}
+
+// One dword (4 samples) of an EO-filtered component: the tile pairs at dwords i0, i0 + 1 and
+// the class neighbours (a +-1 column shift is a v_alignbyte of two pairs); the category index
+// e + 2 of both halves selects the biased offsets with one v_perm.  Neighbours outside the
+// picture (-1) leave the sample as is.
+template <int S>
+__device__ __forceinline__ uint32_t sao_shifted(const uint32_t (&W)[4], int k) {  // pair k shifted by S columns
+  if constexpr (S == 0) return W[k + 1];
+  if constexpr (S < 0) return __builtin_amdgcn_alignbyte(W[k + 1], W[k], 2);
+  if constexpr (S > 0) return __builtin_amdgcn_alignbyte(W[k + 2], W[k + 1], 2);
+}
+template <int CLS, int PD>
+__device__ __forceinline__ uint32_t sao_eo_dword(const uint32_t* t, int i0, uint32_t p) {
+  constexpr int dx = CLS == 1 ? 0 : (CLS == 3 ? 1 : -1), dy = CLS == 0 ? 0 : -1;  // sao_eo_dir
+  const int ra = i0 + dy * PD, rb = i0 - dy * PD;
+  const uint32_t Wa[4] = {t[ra - 1], t[ra], t[ra + 1], t[ra + 2]};
+  const uint32_t Wb[4] = {t[rb - 1], t[rb], t[rb + 1], t[rb + 2]};
+  const uint32_t Cv[2] = {t[i0], t[i0 + 1]};
+  // biased offsets (o + 8) by category index e + 2: bytes {o0, o1, 8 (none), o2 | o3}
+  const uint32_t t0 = ((p >> 7) & 15) | ((p >> 11) & 15) << 8 | 8u << 16 | ((p >> 15) & 15) << 24;
+  const uint32_t t1 = (p >> 19) & 15;
+  const sao_s2 two = {2, 2}, eight = {8, 8};
+  const sao_u2 u8s = {8, 8};
+  uint32_t r2[2];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) tot += bh[cc][band][k];
-    st[cc].bo_n[band] = tot & 2047;
-    st[cc].bo_s[band] = (tot - (tot & 2047)) / 2048;
+  for (int k = 0; k < 2; ++k) {
+    const sao_s2 v = sao_pair(Cv[k]);
+    const sao_s2 A = sao_pair(sao_shifted<dx>(Wa, k)), B = sao_pair(sao_shifted<-dx>(Wb, k));
+    const sao_s2 inv = (A | B) >> 15;  // -1 where a neighbour is outside the picture
+    const sao_s2 e = (sao_sign2(v - A) + sao_sign2(v - B)) & ~inv;
+    const uint32_t sel = __builtin_bit_cast(uint32_t, e + two) | 0x0c000c00u;
+    const sao_s2 off = sao_pair(__builtin_amdgcn_perm(t1, t0, sel));
+    const sao_s2 r = sao_relu2(v + off - eight);  // -7 .. 262 -> 0 .. 262
+    // >= 256 -> low byte 0xFF (only the low byte of each half is kept)
+    r2[k] = __builtin_bit_cast(uint32_t, r | (sao_s2{0, 0} - __builtin_bit_cast(sao_s2, __builtin_bit_cast(sao_u2, r) >> u8s)));
   }
-  __syncthreads();
-  // 144 offset/cost items in parallel (the 96 band items only with band offsets on)
-  if (tid < kSaoItems && (kSaoBandOffsets || tid % 48 < 16)) sao_item(st, lam16, tid, tab);
-  __syncthreads();
-  if (kSaoBandOffsets && tid < 96) sao_window(tid, tab);  // 3 x 32 band windows
-  __syncthreads();
-  if (!kSaoBandOffsets) {
-    if (tid < 3) bpos[tid] = 0;
-  } else if (wave < 3) {  // best band position of component `wave`: first minimum over 32 windows
-    long long j = lane < 32 ? tab.win_j[wave][lane] : LLONG_MAX;
-    int p = lane < 32 ? lane : 64;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const long long j2 = __shfl_xor(j, o);
-      const int p2 = __shfl_xor(p, o);
-      if (j2 < j || (j2 == j && p2 < p)) {
-        j = j2;
-        p = p2;
-      }
-    }
-    if (lane == 0) bpos[wave] = p;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    sao_finish_pos(tab, lam16, bpos, prm);
-    uint32_t* o = sao + 3 * ((long)b * g.wc * g.hc + ctu);
-    o[0] = prm[0];
-    o[1] = prm[1];
-    o[2] = prm[2];
-  }
-  __syncthreads();
-  // the SAO'd CTB from the tile, 4 samples per dword store: luma 32 rows x 8, chroma 16 x 4;
-  // the squared error against the source (display area) is summed on the way (no k_sse).
-  // Packed: the dword's samples are two int16 pairs of the tile (aligned dwords; the EO
-  // neighbours of a +-1 column shift are v_alignbyte of two), the category index e + 2 of
-  // both halves selects the biased offsets with one v_perm, and the squared error is a
-  // v_dot2 of the differences.  Neighbours outside the picture (-1) leave the sample as is.
+  return __builtin_amdgcn_perm(r2[1], r2[0], 0x06040200u);
+}
+// p is wave-uniform: the type and class tests are scalar branches
+template <int PD>
+__device__ __forceinline__ uint32_t sao_filter_dword(const uint32_t* t, int i0, uint32_t p) {
   static_assert(!kSaoBandOffsets, "the SAO filter has no band-offset path");
-  unsigned e2[3] = {0, 0, 0};
-  const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-  for (int i = tid; i < 256 + 128; i += 256) {
-    const int cc = i < 256 ? 0 : (i < 320 ? 1 : 2);
-    const int j = cc == 0 ? i : i - 256 - (cc - 1) * 64;
-    const int nd = cc ? 4 : 8, nn = cc ? 16 : 32, ww = cc ? g.W / 2 : g.W;
-    const int ly = j >> (cc ? 2 : 3), lx0 = 4 * (j & (nd - 1));  // nd = 4 / 8 dwords per row
-    const uint32_t p = prm[cc];
-    const long at = (long)(cy * nn + ly) * ww + cx * nn + lx0;
-    const int dwc = cc ? g.dw / 2 : g.dw, dhc = cc ? g.dh / 2 : g.dh;
-    const bool want_sse = sse && cy * nn + ly < dhc;
-    const uint32_t sw = want_sse ? *reinterpret_cast<const uint32_t*>(src.plane(cc, b, g) + at) : 0u;
-    uint32_t word = 0;
-    const int i0 = sao_tix(cc, ly + 1, lx0 + 1) >> 1;  // pairs (lx0, lx0 + 1), (lx0 + 2, lx0 + 3)
-    const uint32_t C0 = tile32[i0], C1 = tile32[i0 + 1];
-    if (sao_type(p) == 2) {
-      int dx, dy;
-      sao_eo_dir(sao_class(p), dx, dy);
-      const int pd = (cc ? kSaoPc : kSaoP) >> 1;  // dwords per tile row
-      const int ra = i0 + dy * pd, rb = i0 - dy * pd;
-      const uint32_t Wa[4] = {tile32[ra - 1], tile32[ra], tile32[ra + 1], tile32[ra + 2]};
-      const uint32_t Wb[4] = {tile32[rb - 1], tile32[rb], tile32[rb + 1], tile32[rb + 2]};
-      // pair k of a row shifted by s columns (s = -1, 0, 1): dwords W[k .. k + 2] = columns
-      // lx0 + 2k - 2 .. lx0 + 2k + 3
-      auto shifted = [](const uint32_t* W, int k, int s) -> uint32_t {
-        return s == 0 ? W[k + 1] : s < 0 ? __builtin_amdgcn_alignbyte(W[k + 1], W[k], 2)
-                                         : __builtin_amdgcn_alignbyte(W[k + 2], W[k + 1], 2);
-      };
-      // biased offsets (o + 8) by category index e + 2: bytes {o0, o1, 8 (none), o2 | o3}
-      const uint32_t t0 = ((p >> 7) & 15) | ((p >> 11) & 15) << 8 | 8u << 16 | ((p >> 15) & 15) << 24;
-      const uint32_t t1 = (p >> 19) & 15;
-      const sao_s2 two = {2, 2}, eight = {8, 8};
-      const sao_u2 u8s = {8, 8};
-      uint32_t r2[2];
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const sao_s2 v = sao_pair(k ? C1 : C0);
-        const sao_s2 A = sao_pair(shifted(Wa, k, dx)), B = sao_pair(shifted(Wb, k, -dx));
-        const sao_s2 inv = (A | B) >> 15;  // -1 where a neighbour is outside the picture
-        const sao_s2 e = (sao_sign2(v - A) + sao_sign2(v - B)) & ~inv;
-        const uint32_t sel = __builtin_bit_cast(uint32_t, e + two) | 0x0c000c00u;
-        const sao_s2 off = sao_pair(__builtin_amdgcn_perm(t1, t0, sel));
-        const sao_s2 r = sao_relu2(v + off - eight);  // -7 .. 262 -> 0 .. 262
-        // >= 256 -> low byte 0xFF (only the low byte of each half is kept)
-        r2[k] = __builtin_bit_cast(uint32_t, r | (sao_s2{0, 0} - __builtin_bit_cast(sao_s2, __builtin_bit_cast(sao_u2, r) >> u8s)));
-      }
-      word = __builtin_amdgcn_perm(r2[1], r2[0], 0x06040200u);
-    } else {
-      word = __builtin_amdgcn_perm(C1, C0, 0x06040200u);
+  if (sao_type(p) == 2) {
+    switch (sao_class(p)) {
+      case 0: return sao_eo_dword<0, PD>(t, i0, p);
+      case 1: return sao_eo_dword<1, PD>(t, i0, p);
+      case 2: return sao_eo_dword<2, PD>(t, i0, p);
+      default: return sao_eo_dword<3, PD>(t, i0, p);
     }
-    *reinterpret_cast<uint32_t*>(out.plane(cc, b, g) + at) = word;
-    if (want_sse) {
-      if (cx * nn + lx0 + 4 <= dwc) {  // the whole dword is in the display area
+  }
+  return __builtin_amdgcn_perm(t[i0 + 1], t[i0], 0x06040200u);
+}
+// squared error of a dword against the source over the display columns (x0 .. x0 + 3 < dwc)
+__device__ __forceinline__ unsigned sao_sse_dword(uint32_t sw, uint32_t word, int x0, int dwc) {
+  unsigned e2 = 0;
+  if (x0 + 4 <= dwc) {  // the whole dword is in the display area
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const uint32_t sel = h ? 0x0c030c02u : 0x0c010c00u;
-          const sao_s2 d = sao_pair(__builtin_amdgcn_perm(0u, sw, sel)) - sao_pair(__builtin_amdgcn_perm(0u, word, sel));
-          const sao_u2 dd = __builtin_bit_cast(sao_u2, d * d);  // <= 65025 per half
-          e2[cc] = __builtin_amdgcn_udot2(dd, sao_u2{1, 1}, e2[cc], false);
-        }
-      } else {
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t sel = h ? 0x0c030c02u : 0x0c010c00u;
+      const sao_s2 d = sao_pair(__builtin_amdgcn_perm(0u, sw, sel)) - sao_pair(__builtin_amdgcn_perm(0u, word, sel));
+      const sao_u2 dd = __builtin_bit_cast(sao_u2, d * d);  // <= 65025 per half
+      e2 = __builtin_amdgcn_udot2(dd, sao_u2{1, 1}, e2, false);
+    }
+  } else {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int d = (int)((sw >> (8 * q)) & 255) - (int)((word >> (8 * q)) & 255);
-          e2[cc] += cx * nn + lx0 + q < dwc ? (unsigned)(d * d) : 0u;
+    for (int q = 0; q < 4; ++q) {
+      const int d = (int)((sw >> (8 * q)) & 255) - (int)((word >> (8 * q)) & 255);
+      e2 += x0 + q < dwc ? (unsigned)(d * d) : 0u;
+    }
+  }
+  return e2;
+}
+
+// 8 workgroups per CU (8 waves per SIMD): 64 VGPRs, no scratch; the tile is 13.9 KB of LDS.
+__global__ void __launch_bounds__(64 * kSaoStrip, 8) k_sao_decide(FrameSet src, FrameSet deb, FrameSet out, uint32_t* sao,
+                                                               Geo g, const int8_t* qp, const RcTables* rc,
+                                                               unsigned long long* sse) {
+  static_assert(!kSaoBandOffsets, "the statistics carry no band histogram, the decision no band window or argmin");
+  constexpr int S = kSaoStrip;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar CTB logic
+  int strip, b;
+  xcd_ctb(strip, b);
+  const int spr = (g.wc + S - 1) / S;  // strips per CTB row
+  const int sx = strip % spr, cy = strip / spr, cx = sx * S + wave;
+  const bool active = cx < g.wc;
+  const long long lam16 = rc->sao_lam16[qp[b]];
+  __shared__ __align__(16) uint32_t tile[kSaoTileDw];  // luma 34 rows, then Cb, Cr 18 rows each
+  __shared__ unsigned long long esum[3];
+  if (tid < 3) esum[tid] = 0;
+  const int cw = g.W / 2;
+  // statistics lanes: luma pair column p of row group rg (8 rows); chroma plane cp, 4 rows
+  const int rgY = lane >> 4, pY = lane & 15;
+  const int cp = lane >> 5, rgC = (lane >> 3) & 3, pC = lane & 7;
+  uint32_t spY[8];
+  {  // the deblocked strip + ring: wave w stages tile rows w, w + S, ...; a lane takes one plane
+     // dword of the row (luma: lane, chroma: Cb | Cr on the 32-lane halves), so the row base
+     // is a scalar.  A CTB edge is a multiple of 4: a dword is wholly inside or wholly
+     // outside the plane.  Plane dword d of a row covers strip samples 4d - 4 .. 4d - 1 and
+     // lands as two int16 pairs (v_perm) in tile dwords 2d - 1 and 2d; the first plane dword
+     // has only its second pair in the tile, the last only its first.
+    constexpr int nY = (kSaoRows + S - 1) / S, nC = (kSaoRowsC + S - 1) / S;
+    uint32_t vy[nY], vc[nC];
+    bool iy[nY], ic[nC];
+    const int dY = lane, xY = sx * (32 * S) - 4 + 4 * dY;
+    const bool colY = dY < kSaoSrcDw && xY >= 0 && xY < g.W;
+    const uint8_t* PY = deb.plane(0, b, g);
+#pragma unroll
+    for (int i = 0; i < nY; ++i) {
+      const int row = wave + S * i, y = cy * 32 - 1 + row;
+      iy[i] = colY && row < kSaoRows && y >= 0 && y < g.H;
+      vy[i] = iy[i] ? *reinterpret_cast<const uint32_t*>(PY + (long)y * g.W + xY) : 0u;
+    }
+    const int dC = lane & 31, xC = sx * (16 * S) - 4 + 4 * dC;
+    const bool colC = dC < kSaoSrcDwC && xC >= 0 && xC < cw;
+    const uint8_t* PC = deb.plane(1 + cp, b, g);
+#pragma unroll
+    for (int i = 0; i < nC; ++i) {
+      const int row = wave + S * i, y = cy * 16 - 1 + row;
+      ic[i] = colC && row < kSaoRowsC && y >= 0 && y < g.H / 2;
+      vc[i] = ic[i] ? *reinterpret_cast<const uint32_t*>(PC + (long)y * cw + xC) : 0u;
+    }
+    // source pairs of this lane's luma statistics rows, in flight over the staging
+    const uint8_t* SY = src.plane(0, b, g) + (long)(cy * 32 + 8 * rgY) * g.W + cx * 32 + 2 * pY;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) spY[r] = active ? *reinterpret_cast<const uint16_t*>(SY + r * g.W) : 0u;
+#pragma unroll
+    for (int i = 0; i < nY; ++i) {
+      const int row = wave + S * i;
+      if (row >= kSaoRows || dY >= kSaoSrcDw) continue;
+      const uint32_t lo = iy[i] ? __builtin_amdgcn_perm(0u, vy[i], 0x0c010c00u) : 0xFFFFFFFFu;  // outside: -1 pairs
+      const uint32_t hi = iy[i] ? __builtin_amdgcn_perm(0u, vy[i], 0x0c030c02u) : 0xFFFFFFFFu;
+      uint32_t* T = tile + row * kSaoPd + 2 * dY;
+      if (dY >= 1) T[-1] = lo;
+      if (dY < kSaoSrcDw - 1) T[0] = hi;
+    }
+#pragma unroll
+    for (int i = 0; i < nC; ++i) {
+      const int row = wave + S * i;
+      if (row >= kSaoRowsC || dC >= kSaoSrcDwC) continue;
+      const uint32_t lo = ic[i] ? __builtin_amdgcn_perm(0u, vc[i], 0x0c010c00u) : 0xFFFFFFFFu;
+      const uint32_t hi = ic[i] ? __builtin_amdgcn_perm(0u, vc[i], 0x0c030c02u) : 0xFFFFFFFFu;
+      uint32_t* T = tile + kSaoLumaDw + cp * kSaoChromaDw + row * kSaoPdC + 2 * dC;
+      if (dC >= 1) T[-1] = lo;
+      if (dC < kSaoSrcDwC - 1) T[0] = hi;
+    }
+  }
+  __syncthreads();
+  unsigned e2[3] = {0, 0, 0};
+  if (active) {  // wave-uniform: the whole wave is in, the DPP and permlane steps below are safe
+    // A CTB away from the picture edge has no outside (-1) neighbours and skips the masks.
+    const bool interior = cx > 0 && cy > 0 && cx < g.wc - 1 && cy < g.hc - 1;
+    const uint32_t* tY = tile + wave * 16 + 1;                  // dword of the CTB's sample 0 in tile row 0
+    const uint32_t* tC0 = tile + kSaoLumaDw + wave * 8 + 1;     // the same of Cb; Cr + kSaoChromaDw
+    int totY, totC;
+    {
+      sao_u2 acc[4][4];
+      int t[16];
+      uint32_t spC[4];
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[d][q] = sao_u2{0, 0};
+      const uint32_t* tp = tY + 8 * rgY * kSaoPd + pY;
+      if (interior)
+        sao_walk<false, 8, kSaoPd>(tp, spY, acc);
+      else
+        sao_walk<true, 8, kSaoPd>(tp, spY, acc);
+      sao_counters(acc, t);
+      totY = sao_reduce16<false>(t, lane);
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[d][q] = sao_u2{0, 0};
+      tp = tC0 + cp * kSaoChromaDw + 4 * rgC * kSaoPdC + pC;
+      const uint8_t* SC = src.plane(1 + cp, b, g) + (long)(cy * 16 + 4 * rgC) * cw + cx * 16 + 2 * pC;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) spC[r] = *reinterpret_cast<const uint16_t*>(SC + r * cw);
+      if (interior)
+        sao_walk<false, 4, kSaoPdC>(tp, spC, acc);
+      else
+        sao_walk<true, 4, kSaoPdC>(tp, spC, acc);
+      sao_counters(acc, t);
+      totC = sao_reduce16<true>(t, lane);
+    }
+    // The 48 items of the CTB at once: even lanes the luma counter lane >> 2, odd lanes the
+    // counter (lane & 31) >> 1 of Cb (lanes < 32) / Cr; class k >> 2, category (k & 3) + 1.
+    uint32_t prm[3];
+    {
+      const bool chroma = lane & 1;
+      const int tot = chroma ? totC : totY, k = chroma ? (lane & 31) >> 1 : lane >> 2;
+      const int n = tot & 2047, s = (tot - n) >> 11;
+      const bool pos = (k & 3) < 2;  // categories 1, 2 >= 0; 3, 4 <= 0 (tv::sao_item)
+      int o;
+      const long long j = sao_best_offset(n, s, pos ? 0 : -kSaoMaxOff, pos ? kSaoMaxOff : 0, lam16, false, o);
+      const uint32_t ob = (uint32_t)(o + 8) << (7 + 4 * (k & 3));  // the item's field of sao_pack
+      // class sums (tv::sao_eo_j) and offset fields: luma class = 16-lane row (one item on
+      // every fourth lane), chroma (plane, class) = 8-lane group (the odd lanes)
+      const bool ly = (lane & 3) == 0;
+      long long jy = ly ? j : 0, jc = chroma ? j : 0;
+      int py = ly ? (int)ob : 0, pc = chroma ? (int)ob : 0;
+      jy = sao_dpp_add64<dpp::kQuadXor1>(jy);
+      jy = sao_dpp_add64<dpp::kQuadXor2>(jy);
+      jc = sao_dpp_add64<dpp::kQuadXor1>(jc);
+      jc = sao_dpp_add64<dpp::kQuadXor2>(jc);
+      jy = sao_dpp_add64<dpp::kRowHalfMirror>(jy);
+      jc = sao_dpp_add64<dpp::kRowHalfMirror>(jc);
+      jy = sao_dpp_add64<dpp::kRowMirror>(jy);
+      py += dpp::mov<dpp::kQuadXor1>(py);
+      py += dpp::mov<dpp::kQuadXor2>(py);
+      pc += dpp::mov<dpp::kQuadXor1>(pc);
+      pc += dpp::mov<dpp::kQuadXor2>(pc);
+      py += dpp::mov<dpp::kRowHalfMirror>(py);
+      pc += dpp::mov<dpp::kRowHalfMirror>(pc);
+      py += dpp::mov<dpp::kRowMirror>(py);
+      // the choices of tv::sao_finish_pos on scalars.  Rate in bits: type 1 (off) / 2 (edge), class 2.
+      long long best = lam16 * 1;
+      int cls = -1;
+#pragma unroll
+      for (int c2 = 0; c2 < 4; ++c2) {
+        const long long jj = sao_readlane64(jy, 16 * c2) + lam16 * 4;
+        if (jj < best) {
+          best = jj;
+          cls = c2;
         }
       }
+      prm[0] = cls < 0 ? sao_off_param() : 2u | (uint32_t)cls << 2 | (uint32_t)__builtin_amdgcn_readlane(py, 16 * cls);
+      best = lam16 * 1;
+      cls = -1;
+#pragma unroll
+      for (int c2 = 0; c2 < 4; ++c2) {  // one type (and EO class) for Cb and Cr
+        const long long jj = sao_readlane64(jc, 8 * c2) + sao_readlane64(jc, 32 + 8 * c2) + lam16 * 4;
+        if (jj < best) {
+          best = jj;
+          cls = c2;
+        }
+      }
+      prm[1] = cls < 0 ? sao_off_param() : 2u | (uint32_t)cls << 2 | (uint32_t)__builtin_amdgcn_readlane(pc, 8 * cls);
+      prm[2] = cls < 0 ? sao_off_param() : 2u | (uint32_t)cls << 2 | (uint32_t)__builtin_amdgcn_readlane(pc, 32 + 8 * cls);
+      if (lane < 3) sao[3 * ((long)b * g.wc * g.hc + cy * g.wc + cx) + lane] = lane == 0 ? prm[0] : (lane == 1 ? prm[1] : prm[2]);
+    }
+    // the SAO'd CTB from the tile, 4 samples per dword store: luma 32 rows x 8 dwords (4 per
+    // lane), chroma 16 x 4 (one per lane and plane); the squared error against the source
+    // (display area) is summed on the way (no k_sse).  The 8 / 4 lanes of a row segment are
+    // adjacent; the rows of a 32-lane half are 8 (luma) / 4 (chroma) apart, which spreads
+    // their tile reads over the banks.
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int ly = 8 * ((lane >> 3) & 3) + 4 * (lane >> 5) + k, lx0 = 4 * (lane & 7);
+      const long at = (long)(cy * 32 + ly) * g.W + cx * 32 + lx0;
+      const bool want_sse = sse && cy * 32 + ly < g.dh;
+      const uint32_t sw = want_sse ? *reinterpret_cast<const uint32_t*>(src.plane(0, b, g) + at) : 0u;
+      const uint32_t word = sao_filter_dword<kSaoPd>(tY, (ly + 1) * kSaoPd + (lx0 >> 1), prm[0]);
+      *reinterpret_cast<uint32_t*>(out.plane(0, b, g) + at) = word;
+      if (want_sse) e2[0] += sao_sse_dword(sw, word, cx * 32 + lx0, g.dw);
+    }
+#pragma unroll
+    for (int cc = 1; cc < 3; ++cc) {
+      const int ly = 4 * ((lane >> 2) & 3) + (lane >> 4), lx0 = 4 * (lane & 3);
+      const long at = (long)(cy * 16 + ly) * cw + cx * 16 + lx0;
+      const bool want_sse = sse && cy * 16 + ly < g.dh / 2;
+      const uint32_t sw = want_sse ? *reinterpret_cast<const uint32_t*>(src.plane(cc, b, g) + at) : 0u;
+      const uint32_t word =
+          sao_filter_dword<kSaoPdC>(tC0 + (cc - 1) * kSaoChromaDw, (ly + 1) * kSaoPdC + (lx0 >> 1), prm[cc]);
+      *reinterpret_cast<uint32_t*>(out.plane(cc, b, g) + at) = word;
+      if (want_sse) e2[cc] += sao_sse_dword(sw, word, cx * 16 + lx0, g.dw / 2);
     }
   }
   if (sse) {
-    __shared__ unsigned long long esum[3];
-    if (tid < 3) esum[tid] = 0;
-    __syncthreads();
+    if (active) {
 #pragma unroll
-    for (int c2 = 0; c2 < 3; ++c2) {
-      const int t = wave_sum((int)e2[c2]);  // <= 2 dwords x 4 x 65025 per lane: fits
-      if (lane == 0 && t) atomicAdd(&esum[c2], (unsigned long long)(unsigned)t);
+      for (int c2 = 0; c2 < 3; ++c2) {
+        const int t = wave_sum((int)e2[c2]);  // <= 4 dwords x 4 x 65025 per lane: fits
+        if (lane == 0 && t) atomicAdd(&esum[c2], (unsigned long long)(unsigned)t);
+      }
     }
     __syncthreads();
     if (tid < 3 && esum[tid]) atomicAdd(sse + b * 3 + tid, esum[tid]);
@@ -981,7 +1036,8 @@ __global__ void __launch_bounds__(256) k_sao_decide(FrameSet src, FrameSet deb, 
 
 void launch_sao(FrameSet src, FrameSet deb, FrameSet out, uint32_t* sao, const int8_t* qp, const RcTables* rc,
                 const Geo& g, int B, hipStream_t s, unsigned long long* sse) {
-  k_sao_decide<<<dim3(g.wc * g.hc, B), 256, 0, s>>>(src, deb, out, sao, g, qp, rc, sse);
+  const int strips = (g.wc + kSaoStrip - 1) / kSaoStrip * g.hc;
+  k_sao_decide<<<dim3(strips, B), 64 * kSaoStrip, 0, s>>>(src, deb, out, sao, g, qp, rc, sse);
 }
 
 void launch_deblock(FrameSet rec, DecisionSet dec, const Geo& g, int B, hipStream_t s) {

@@ -10,6 +10,7 @@
 //  k_pad_plane   display-size plane -> coded-size plane with edge replication, batched
 //  tv_synth_batch  the seeded synthetic source (tv/synth.h) generated for n frames on the
 //                  GPU at coded size in planar-batched layout (Y of every frame, then U, V)
+//  tv_sao_batch    the engine's SAO kernel (k_sao_decide) on device pictures of that layout
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -113,5 +114,49 @@ int tv_synth_batch(uint8_t* dst, int w, int h, int n, const int* t, uint32_t see
     tv::gpu::launch_synth(fs, g, seed, fi, B, static_cast<hipStream_t>(stream));
   }
   return stage_status();
+}
+
+// SAO of B deblocked pictures against their sources (k_sao_decide as the engine launches it):
+// src, deb, out are w x h (display) pictures at coded size, planar-batched like tv_synth_batch;
+// qp: B slice QPs in host memory.  Writes B x (CTBs x 3) packed parameters, the filtered
+// pictures and B x 3 display-area SSE sums (device pointers); returns after the stream is idle.
+int tv_sao_batch(const uint8_t* src, const uint8_t* deb, uint8_t* out, uint32_t* sao, unsigned long long* sse, int w,
+                 int h, int B, const int8_t* qp, void* stream) {
+  if (w < 2 || h < 2 || (w & 1) || (h & 1) || B <= 0 || B > tv::gpu::kMaxBatch) {
+    g_stage_err = "tv_sao_batch: bad geometry";
+    return -1;
+  }
+  for (int b = 0; b < B; ++b)
+    if (qp[b] < 0 || qp[b] > 51) {
+      g_stage_err = "tv_sao_batch: bad QP";
+      return -1;
+    }
+  using namespace tv::gpu;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Geo g = make_geo(w, h);
+  auto set = [&](const uint8_t* p) {
+    uint8_t* q = const_cast<uint8_t*>(p);
+    return FrameSet{q, q + B * g.ysz, q + B * g.ysz + B * g.csz};
+  };
+  RcTables t{};  // the decision constants of every QP, as the engine fills them
+  for (int q = 0; q < 52; ++q) t.sao_lam16[q] = tv::sao_lambda16(q);
+  RcTables* rc = nullptr;
+  int8_t* dqp = nullptr;
+  bool ok = hipMalloc(&rc, sizeof(RcTables)) == hipSuccess && hipMalloc(&dqp, (size_t)B) == hipSuccess &&
+            hipMemcpyAsync(rc, &t, sizeof(RcTables), hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemcpyAsync(dqp, qp, (size_t)B, hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemsetAsync(sse, 0, (size_t)B * 3 * sizeof(unsigned long long), st) == hipSuccess;
+  if (ok) {
+    launch_sao(set(src), set(deb), set(out), sao, dqp, rc, g, B, st, sse);
+    ok = hipStreamSynchronize(st) == hipSuccess;
+  }
+  const int rcode = stage_status();
+  (void)hipFree(rc);
+  (void)hipFree(dqp);
+  if (rcode == 0 && !ok) {
+    g_stage_err = "tv_sao_batch: device error";
+    return -1;
+  }
+  return rcode;
 }
 }

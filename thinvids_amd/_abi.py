@@ -37,6 +37,7 @@ CORE = {
     "tv_synth_frame": (None, [u32, i, i, i, u8p, u8p, u8p]),
     "tv_synth_frame_tiled": (None, [u32, i, i, i, i, i, u8p, u8p, u8p]),
     "tv_satd8x8": (i, [i32p, i]),
+    "tv_sao_picture_cpu": (i, [i, i, i] + [u8p] * 6 + [u32p] + [u8p] * 3),
     # HEVC golden encoder
     "tv_cpu_encoder_new": (vp, [i] * 6),
     "tv_cpu_encoder_new_b": (vp, [i] * 7),
@@ -147,6 +148,7 @@ GPU = {
     "tv_thumbs8_batch": (i, [vp, i, i, i, i, l, i, vp, vp]),
     "tv_pad_batch": (i, [vp, i, i, i, l, vp, i, i, i, l, i, vp]),
     "tv_synth_batch": (i, [vp, i, i, i, i32p, u32, vp]),
+    "tv_sao_batch": (i, [vp, vp, vp, vp, vp, i, i, i, i8p, vp]),
     # k_ops.hip: every pointer is a device pointer or the stream, but the bwdif plane tables
     "tv_ops_last_error": (cstr, []),
     "tv_resize_plane": (i, [vp, i, i, i, vp, i, i, i, vp, vp, i, vp, vp, i, vp, vp]),

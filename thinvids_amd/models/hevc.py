@@ -29,6 +29,20 @@ def synth_frame(seed: int, t: int, width: int, height: int) -> Frame:
     return y, u, v
 
 
+def sao_picture_cpu(src: Frame, deb: Frame, qp: int) -> tuple[np.ndarray, Frame]:
+    """The golden SAO of one coded-size picture: per-CTB parameters ``[CTB rows, CTB columns, 3]``
+    decided from the deblocked planes against the source at slice QP `qp`, and the filtered
+    picture."""
+    h, w = deb[0].shape
+    src = [np.ascontiguousarray(p, np.uint8) for p in src]
+    deb = [np.ascontiguousarray(p, np.uint8) for p in deb]
+    params = np.empty((h // 32, w // 32, 3), np.uint32)
+    out = [np.empty_like(p) for p in deb]
+    check(core_lib().tv_sao_picture_cpu(w, h, qp, *[ptr(p) for p in src], *[ptr(p) for p in deb], ptr(params),
+                                        *[ptr(p) for p in out]))
+    return params, tuple(out)
+
+
 def psnr(a: np.ndarray, b: np.ndarray) -> float:
     mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
     return float("inf") if mse == 0 else 10.0 * np.log10(255.0 ** 2 / mse)

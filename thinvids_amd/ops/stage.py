@@ -136,6 +136,39 @@ def synth_frames(seed: int, w: int, h: int, starts, device) -> DevFrames:
     return DevFrames(buf, n, w, h, planes, 8)
 
 
+def sao_pictures(src, deb, w: int, h: int, qps, device):
+    """The engine's SAO kernel on its own: `src` / `deb` are lists of B coded-size (Y, U, V)
+    host pictures (source, deblocked) of a w x h display, `qps` their slice QPs.  Returns
+    the packed parameters ``[B, CTB rows, CTB columns, 3]`` (uint32), the B filtered
+    pictures and the display-area SSE sums ``[B, 3]`` (uint64) as numpy arrays."""
+    import torch
+
+    B = len(deb)
+    cw, ch = coded_size(w, h)
+
+    def batched(pics):  # planar-batched: the Y planes of every picture, then U, then V
+        flat = np.concatenate([np.ascontiguousarray(p[c], np.uint8).reshape(-1) for c in range(3) for p in pics])
+        assert flat.size == B * cw * ch * 3 // 2, "pictures must have the coded size"
+        return torch.from_numpy(flat).to(device)
+
+    ds, dd = batched(src), batched(deb)
+    out = torch.empty_like(dd)
+    nctb = (cw // 32) * (ch // 32)
+    prm = torch.empty(B * nctb * 3, dtype=torch.int32, device=device)
+    sse = torch.empty(B * 3, dtype=torch.int64, device=device)
+    q = (C.c_int8 * B)(*[int(x) for x in qps])
+    torch.cuda.current_stream(device).synchronize()
+    _ok(_lib().tv_sao_batch(ds.data_ptr(), dd.data_ptr(), out.data_ptr(), prm.data_ptr(), sse.data_ptr(), w, h, B, q,
+                            stream(device)))
+    o = out.cpu().numpy()
+    ysz, csz = cw * ch, cw * ch // 4
+    pics = [(o[b * ysz:(b + 1) * ysz].reshape(ch, cw),
+             o[B * ysz + b * csz:B * ysz + (b + 1) * csz].reshape(ch // 2, cw // 2),
+             o[B * (ysz + csz) + b * csz:B * (ysz + csz) + (b + 1) * csz].reshape(ch // 2, cw // 2)) for b in range(B)]
+    return (prm.cpu().numpy().view(np.uint32).reshape(B, ch // 32, cw // 32, 3), pics,
+            sse.cpu().numpy().view(np.uint64).reshape(B, 3))
+
+
 def tone_map(src: DevFrames, src_peak: float = 1000.0, dst_peak: float = 100.0) -> DevFrames:
     """10-bit planar PQ (BT.2020) -> 8-bit SDR BT.709 I420 on the device (k_tonemap_pq)."""
     import torch
