@@ -89,40 +89,24 @@ void analyze_intra(const SeqConfig& cfg, const Picture& src, FrameDecisions& fd)
   auto best_mode = [&](int x, int y, int log2) -> Best { return intra_best_mode(src, W, lam, x, y, log2, pred); };
   for (int cy = 0; cy < H; cy += 32)
     for (int cx = 0; cx < W; cx += 32) {
-      // bottom-up quadtree on source-based costs
-      const Best b32 = best_mode(cx, cy, 5);
-      int sum16 = 0;
-      int split16[4];
-      Best b16s[4];
-      for (int q = 0; q < 4; ++q) {
-        const int x = cx + (q & 1) * 16, y = cy + (q >> 1) * 16;
-        const Best b16 = best_mode(x, y, 4);
-        int sum8 = 0;
-        Best b8s[4];
-        for (int r = 0; r < 4; ++r) {
-          b8s[r] = best_mode(x + (r & 1) * 8, y + (r >> 1) * 8, 3);
-          sum8 += b8s[r].cost + (int)(lam * 3);
-        }
-        split16[q] = sum8 < b16.cost + (int)(lam * 3);
-        b16s[q] = b16;
-        const int c16 = split16[q] ? sum8 : b16.cost + (int)(lam * 3);
-        sum16 += c16;
-        for (int r = 0; r < 4; ++r) {
-          const int u = ((y >> 3) + (r >> 1)) * fd.w8 + (x >> 3) + (r & 1);
-          fd.cu_log2[u] = split16[q] ? 3 : 4;
-          fd.ipm[u] = (uint8_t)(split16[q] ? b8s[r].mode : b16.mode);
-        }
+      // bottom-up quadtree on the source-based costs of the CTB's 21 blocks
+      int cost[21], mode[21];
+      for (int bi = 0; bi < 21; ++bi) {
+        int bx, by, l2b;
+        me_blk_geom(bi, bx, by, l2b);
+        const Best bb = best_mode(cx + bx, cy + by, l2b);
+        cost[bi] = bb.cost;
+        mode[bi] = bb.mode;
       }
-      if (b32.cost + (int)(lam * 3) <= sum16) {
-        for (int j = 0; j < 4; ++j)
-          for (int i = 0; i < 4; ++i) {
-            const int u = ((cy >> 3) + j) * fd.w8 + (cx >> 3) + i;
-            fd.cu_log2[u] = 5;
-            fd.ipm[u] = (uint8_t)b32.mode;
-          }
+      int sel[16];
+      uint8_t l2[16];
+      split_ctb(cost, (int)(lam * 3), sel, l2);
+      for (int k = 0; k < 16; ++k) {
+        const int u = ((cy >> 3) + (k >> 2)) * fd.w8 + (cx >> 3) + (k & 3);
+        fd.cu_log2[u] = l2[k];
+        fd.ipm[u] = (uint8_t)mode[sel[k]];
+        fd.intra[u] = 1;
       }
-      for (int j = 0; j < 4; ++j)
-        for (int i = 0; i < 4; ++i) fd.intra[((cy >> 3) + j) * fd.w8 + (cx >> 3) + i] = 1;
     }
 }
 
@@ -166,18 +150,6 @@ void coarse_search(const uint8_t* qcur, const uint8_t* qprev, int W, int H, int 
 }
 
 namespace {
-// block geometry of the 21 ME blocks: 16 x 8x8 (raster), 4 x 16x16, 1 x 32x32
-void me_blk(int bi, int& bx, int& by, int& n) {
-  if (bi < 16) {
-    bx = (bi & 3) * 8, by = (bi >> 2) * 8, n = 8;
-  } else if (bi < 20) {
-    bx = ((bi - 16) & 1) * 16, by = ((bi - 16) >> 1) * 16, n = 16;
-  } else {
-    bx = by = 0, n = 32;
-  }
-}
-int me_blk8_of(int q, int r) { return (((q >> 1) * 2 + (r >> 1)) << 2) + (q & 1) * 2 + (r & 1); }
-
 // Motion search of one CTB against one reference: the 21 blocks' best cost (SAD + MV rate),
 // vector and rate part (the GPU's k_inter_me computes exactly this).
 struct CtbMe {
@@ -253,8 +225,9 @@ void me_ctb(const SeqConfig& cfg, const Picture& src, const Picture& ref, const 
     bmv[0] = 4 * mx;
     bmv[1] = 4 * my;
     out.cost[bi] = (int)(best[bi] >> 11);
-    int bx, by, n;
-    me_blk(bi, bx, by, n);
+    int bx, by, l2b;
+    me_blk_geom(bi, bx, by, l2b);
+    const int n = 1 << l2b;
     if (cfg.subpel_satd) {
       // the SATD sub-pel decision of tv/me_model.h: J = SATD + MV rate picks the vector, the
       // reported cost stays SAD + MV rate at that vector
@@ -297,28 +270,6 @@ void me_ctb(const SeqConfig& cfg, const Picture& src, const Picture& ref, const 
     }
     out.pen[bi] = penmv[me_pen_index(bmv[0] - pmv[0], bmv[1] - pmv[1])];
   }
-}
-
-// Bottom-up CU split of one CTB from per-block costs; writes cu_log2 and the block's index
-// into `sel` per 8x8 unit (the caller copies that block's motion).
-void split_ctb(const int* bcost, int pen_split, int sel[16], uint8_t l2[16]) {
-  int sum16 = 0;
-  for (int q = 0; q < 4; ++q) {
-    int sum8 = 0;
-    for (int r = 0; r < 4; ++r) sum8 += bcost[me_blk8_of(q, r)] + pen_split;
-    const bool split = sum8 < bcost[16 + q] + pen_split;
-    sum16 += split ? sum8 : bcost[16 + q] + pen_split;
-    for (int r = 0; r < 4; ++r) {
-      const int ux = (q & 1) * 2 + (r & 1), uy = (q >> 1) * 2 + (r >> 1);
-      sel[uy * 4 + ux] = split ? me_blk8_of(q, r) : 16 + q;
-      l2[uy * 4 + ux] = split ? 3 : 4;
-    }
-  }
-  if (bcost[20] + pen_split <= sum16)
-    for (int k = 0; k < 16; ++k) {
-      sel[k] = 20;
-      l2[k] = 5;
-    }
 }
 }  // namespace
 
@@ -419,9 +370,9 @@ void analyze_inter_b(const SeqConfig& cfg, const Picture& src, const Picture& re
       me_ctb(cfg, src, ref1, cmv1, prev_mv, range[1], cxi, cyi, fd.w8, m1);
       int cost[21], dir[21];
       for (int bi = 0; bi < 21; ++bi) {
-        int bx, by, n;
-        me_blk(bi, bx, by, n);
-        const int cb = bipred_sad(src, ref0, ref1, cx + bx, cy + by, n, m0.mv[bi], m1.mv[bi]) + m0.pen[bi] + m1.pen[bi];
+        int bx, by, l2b;
+        me_blk_geom(bi, bx, by, l2b);
+        const int cb = bipred_sad(src, ref0, ref1, cx + bx, cy + by, 1 << l2b, m0.mv[bi], m1.mv[bi]) + m0.pen[bi] + m1.pen[bi];
         cost[bi] = m0.cost[bi];
         dir[bi] = 1;
         if (m1.cost[bi] < cost[bi]) {

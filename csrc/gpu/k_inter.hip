@@ -72,23 +72,6 @@ __device__ __forceinline__ int win_word(int k, int r, int w) { return k * kWinCa
 constexpr int kSrcP = 8, kSrcSkew = 8;
 __device__ __forceinline__ int src_word(int row, int w) { return row * kSrcP + w + (row >> 3) * kSrcSkew; }
 
-__device__ __forceinline__ void me_blk_geom(int bi, int& bx, int& by, int& l2) {
-  if (bi < 16) {
-    bx = (bi & 3) * 8;
-    by = (bi >> 2) * 8;
-    l2 = 3;
-  } else if (bi < 20) {
-    bx = ((bi - 16) & 1) * 16;
-    by = ((bi - 16) >> 1) * 16;
-    l2 = 4;
-  } else {
-    bx = by = 0;
-    l2 = 5;
-  }
-}
-__device__ __forceinline__ int me_blk8_of(int q, int r) {
-  return (((q >> 1) * 2 + (r >> 1)) << 2) + (q & 1) * 2 + (r & 1);
-}
 // tv::dequant_level in 32-bit arithmetic: with m = 16 * levelScale << (qp / 6) and the level
 // clamped to +-thr, where thr * m is at least (32768 + 1) << bdShift, a clamped level still
 // saturates to the same int16 bound and every unclamped product fits in 32 bits -- the same
@@ -851,6 +834,7 @@ __global__ void __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu
     return;
   }
   // ------------------------------- CU split decision ------------------------------------
+  // the rule of tv::split_ctb (tv/me_model.h), lane-parallel:
   // one lane per 8x8 unit k (raster): every lane forms the same quadrant / CTB sums from the
   // 21 block costs (the same order of additions as the serial form), then writes its unit
   if (tid < 16) {
@@ -977,7 +961,7 @@ __global__ void __launch_bounds__(256) k_bi_decide(FrameSet src, const uint8_t* 
     dirb[tid] = d;
   }
   __syncthreads();
-  if (tid < 4) {
+  if (tid < 4) {  // the rule of tv::split_ctb (tv/me_model.h), a lane per quadrant, then per unit
     int sum8 = 0;
     for (int r = 0; r < 4; ++r) sum8 += cost[me_blk8_of(tid, r)] + ps;
     const bool split = sum8 < cost[16 + tid] + ps;

@@ -10,29 +10,13 @@
 #include "gpu_common.h"
 #include "k_encode.h"
 #include "tb_coder.h"
+#include "wave_intra.h"
 #include "wave_tb.h"
 #include "tv/me_model.h"
 
 namespace tv {
 namespace gpu {
 
-__device__ __forceinline__ void blk_geom(int bi, int& bx, int& by, int& l2) {
-  if (bi < 16) {
-    bx = (bi & 3) * 8;
-    by = (bi >> 2) * 8;
-    l2 = 3;
-  } else if (bi < 20) {
-    bx = ((bi - 16) & 1) * 16;
-    by = ((bi - 16) >> 1) * 16;
-    l2 = 4;
-  } else {
-    bx = by = 0;
-    l2 = 5;
-  }
-}
-__device__ __forceinline__ int blk8_of(int q, int r) {
-  return (((q >> 1) * 2 + (r >> 1)) << 2) + (q & 1) * 2 + (r & 1);
-}
 // flattened reference-sample entry e (0..468) -> (block, index within 2N+1)
 __device__ __forceinline__ void ref_entry(int e, int& bi, int& i) {
   if (e < 272) {
@@ -46,18 +30,6 @@ __device__ __forceinline__ void ref_entry(int e, int& bi, int& i) {
     i = e - 404;
   }
 }
-
-// the angular-mode tables in LDS (indexed constexpr tables become global loads on the GPU)
-struct AngleLds {
-  int8_t angle[35];
-  int16_t inv[35];
-  __device__ void load(int tid, int nthreads) {
-    for (int m = tid; m < 35; m += nthreads) {
-      angle[m] = m >= 2 ? (int8_t)intra_angle(m) : 0;
-      inv[m] = m >= 2 ? (int16_t)intra_inv_angle(m) : 0;
-    }
-  }
-};
 
 __global__ void __launch_bounds__(256) k_intra_analysis(FrameSet src, DecisionSet dec, Geo g, const RcTables* rc) {
   const int ctu = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -76,25 +48,13 @@ __global__ void __launch_bounds__(256) k_intra_analysis(FrameSet src, DecisionSe
   for (int e = tid; e < 469; e += 256) {
     int bi, i, bx, by, l2;
     ref_entry(e, bi, i);
-    blk_geom(bi, bx, by, l2);
-    const int x = cx + bx, y = cy + by;
-    if (i == 0) {
-      const bool a = zscan_available(x, y, x - 1, y - 1, g.W, g.H);
-      avl[bi][0][0] = avl[bi][1][0] = a;
-      refs[bi][0][0] = refs[bi][1][0] = a ? S[(y - 1) * g.W + x - 1] : 0;
-    } else {
-      const bool al = zscan_available(x, y, x - 1, y + i - 1, g.W, g.H);
-      avl[bi][0][i] = al;
-      refs[bi][0][i] = al ? S[(y + i - 1) * g.W + x - 1] : 0;
-      const bool at = zscan_available(x, y, x + i - 1, y - 1, g.W, g.H);
-      avl[bi][1][i] = at;
-      refs[bi][1][i] = at ? S[(y - 1) * g.W + x + i - 1] : 0;
-    }
+    me_blk_geom(bi, bx, by, l2);
+    src_ref_entry(S, g.W, g.H, cx + bx, cy + by, i, refs[bi][0], refs[bi][1], avl[bi][0], avl[bi][1]);
   }
   __syncthreads();
   if (tid < 21) {
     int bx, by, l2;
-    blk_geom(tid, bx, by, l2);
+    me_blk_geom(tid, bx, by, l2);
     intra_substitute(refs[tid][0], refs[tid][1], avl[tid][0], avl[tid][1], 1 << l2);
     dcv[tid] = intra_dc_value(refs[tid][0], refs[tid][1], l2);
   }
@@ -102,19 +62,8 @@ __global__ void __launch_bounds__(256) k_intra_analysis(FrameSet src, DecisionSe
   for (int e = tid; e < 469; e += 256) {  // [1 2 1] smoothed copies
     int bi, i, bx, by, l2;
     ref_entry(e, bi, i);
-    blk_geom(bi, bx, by, l2);
-    const int N2 = 2 << l2;
-    const int16_t* L = refs[bi][0];
-    const int16_t* T = refs[bi][1];
-    if (i == 0) {
-      refs[bi][2][0] = refs[bi][3][0] = (int16_t)((L[1] + 2 * L[0] + T[1] + 2) >> 2);
-    } else if (i == N2) {
-      refs[bi][2][i] = L[i];
-      refs[bi][3][i] = T[i];
-    } else {
-      refs[bi][2][i] = (int16_t)((L[i + 1] + 2 * L[i] + L[i - 1] + 2) >> 2);
-      refs[bi][3][i] = (int16_t)((T[i + 1] + 2 * T[i] + T[i - 1] + 2) >> 2);
-    }
+    me_blk_geom(bi, bx, by, l2);
+    intra_smooth_entry(refs[bi][0], refs[bi][1], refs[bi][2], refs[bi][3], i, 2 << l2);
   }
   __syncthreads();
   const int wave = tid >> 6, lane = tid & 63;
@@ -122,7 +71,7 @@ __global__ void __launch_bounds__(256) k_intra_analysis(FrameSet src, DecisionSe
   // +-1 / +-2 neighbours of each block's best stage-1 angular mode (tv/me_model.h)
   auto eval = [&](int bi, int mode, bool coarse) {
     int bx, by, l2;
-    blk_geom(bi, bx, by, l2);
+    me_blk_geom(bi, bx, by, l2);
     const int N = 1 << l2, nq = N >> 3;
     const bool filt = intra_filter_refs(l2, mode);
     const int16_t* L = refs[bi][filt ? 2 : 0];
@@ -133,7 +82,7 @@ __global__ void __launch_bounds__(256) k_intra_analysis(FrameSet src, DecisionSe
       const int p = intra_pred_pixel_ai(L, T, l2, mode, ang.angle[mode], ang.inv[mode], N < 32, dcv[bi], qx, qy);
       sum += wave_satd8x8((int)sblk[(by + qy) * 32 + bx + qx] - p);
     }
-    const unsigned v = ((unsigned)(sum + (mode <= 1 ? pen.mode_dcpl : pen.mode_ang)) << 6) | (unsigned)mode;
+    const unsigned v = intra_cost_key(sum, mode, pen);
     if (lane == 0) {
       atomicMin(&best[bi], v);
       // only stage 1 moves the refinement centre: stage-2 waves read it concurrently
@@ -148,27 +97,14 @@ __global__ void __launch_bounds__(256) k_intra_analysis(FrameSet src, DecisionSe
   }
   __syncthreads();
   if (tid == 0) {
-    const int ps = pen.split_intra;
-    const int c32 = (int)(best[20] >> 6);
-    int sum16 = 0;
-    uint8_t l2u[16], mu[16];
-    for (int q = 0; q < 4; ++q) {
-      const int c16 = (int)(best[16 + q] >> 6);
-      int sum8 = 0;
-      for (int r = 0; r < 4; ++r) sum8 += (int)(best[blk8_of(q, r)] >> 6) + ps;
-      const bool split = sum8 < c16 + ps;
-      sum16 += split ? sum8 : c16 + ps;
-      for (int r = 0; r < 4; ++r) {
-        const int ux = (q & 1) * 2 + (r & 1), uy = (q >> 1) * 2 + (r >> 1);
-        l2u[uy * 4 + ux] = split ? 3 : 4;
-        mu[uy * 4 + ux] = (uint8_t)(split ? (best[blk8_of(q, r)] & 63) : (best[16 + q] & 63));
-      }
-    }
-    const bool whole = c32 + ps <= sum16;
+    int cost[21], sel[16];
+    uint8_t l2u[16];
+    for (int bi = 0; bi < 21; ++bi) cost[bi] = (int)(best[bi] >> 6);
+    split_ctb(cost, pen.split_intra, sel, l2u);
     for (int k = 0; k < 16; ++k) {
       const long u = b * g.usz + (long)((cy >> 3) + (k >> 2)) * g.w8 + (cx >> 3) + (k & 3);
-      dec.cu_log2[u] = whole ? 5 : l2u[k];
-      dec.ipm[u] = whole ? (uint8_t)(best[20] & 63) : mu[k];
+      dec.cu_log2[u] = l2u[k];
+      dec.ipm[u] = (uint8_t)(best[sel[k]] & 63);
       dec.intra[u] = 1;
       dec.mv[2 * u] = dec.mv[2 * u + 1] = 0;
     }
@@ -193,11 +129,9 @@ struct CompLdsT {
   uint8_t left[S];         // column x = cx-1, y = cy .. cy+S-1
   uint8_t pred[S * S];
   int16_t resid[S * S];
-  int V[4 * S + 4];
-  int L[2 * S + 1], T[2 * S + 1], FL[2 * S + 1], FT[2 * S + 1];
+  IntraRefsT<S> refs;
   WaveTbScratchT<S> tb;
 };
-using CompLds = CompLdsT<32>;
 
 // kSdh (SeqConfig::sign_hiding): wave_code_tb<true> adjusts the levels for sign data hiding.
 template <bool kSdh>
@@ -269,81 +203,16 @@ __global__ void __launch_bounds__(192) k_intra_recon(FrameSet src, FrameSet rec,
   for (int k = 0; k < ncu; ++k) {
     const int x0 = cus[k][0], y0 = cus[k][1], log2 = cus[k][2];
     const int mode = cus[k][3];
-    const int l2 = log2 - sh, N = 1 << l2;
+    const int l2 = log2 - sh;
     const int x = x0 >> sh, y = y0 >> sh;  // TB position (component samples)
-    // --- reference samples in canonical order (bottom-left .. corner .. top-right)
-    const int total = 4 * N + 1;
-    // one round = 64 reference positions; the common 8x8 / 4x4 TBs (4N+1 <= 64) need one
-    auto round = [&](int r) -> unsigned long long {
-      const int i = lane + 64 * r;
-      bool av = false;
-      if (i < total) {
-        int xn, yn;
-        if (i < 2 * N) {
-          xn = x - 1;
-          yn = y + 2 * N - 1 - i;
-        } else {
-          xn = x - 1 + (i - 2 * N);
-          yn = y - 1;
-        }
-        av = zscan_available(x0, y0, xn << sh, yn << sh, g.W, g.H);
-        int val = 0;
-        if (av) {
-          if (xn >= bx && yn >= by) val = L.rec[(yn - by) * S + (xn - bx)];
-          else if (yn == by - 1) val = L.top[xn - (bx - 1)];
-          else val = L.left[yn - by];
-        }
-        L.V[i] = val;
-      }
-      return __ballot(av);
-    };
-    unsigned long long m[3] = {round(0), 0, 0};
-    if (total > 64) m[1] = round(1);
-    if (total > 128) m[2] = round(2);
-    wave_sync();
-    // --- substitution (H.265 8.4.4.2.2) as a parallel nearest-available search
-    for (int i = lane; i < total; i += 64) {
-      int j = -1;
-      for (int w = i >> 6; w >= 0 && j < 0; --w) {
-        const unsigned long long mm =
-            (w == (i >> 6)) ? (m[w] & (((i & 63) == 63) ? ~0ull : ((2ull << (i & 63)) - 1))) : m[w];
-        if (mm) j = w * 64 + 63 - __clzll(mm);
-      }
-      if (j < 0)
-        for (int w = 0; w < 3 && j < 0; ++w)
-          if (m[w]) j = w * 64 + __ffsll(m[w]) - 1;
-      const int v = j < 0 ? 128 : L.V[j];
-      if (i < 2 * N) L.L[2 * N - i] = v;
-      else if (i == 2 * N) L.L[0] = L.T[0] = v;
-      else L.T[i - 2 * N] = v;
-    }
-    wave_sync();
-    const bool filt = c == 0 && intra_filter_refs(l2, mode);
-    if (filt) {
-      for (int i = lane; i <= 2 * N; i += 64) {
-        if (i == 0) {
-          L.FL[0] = L.FT[0] = (L.L[1] + 2 * L.L[0] + L.T[1] + 2) >> 2;
-        } else if (i == 2 * N) {
-          L.FL[i] = L.L[i];
-          L.FT[i] = L.T[i];
-        } else {
-          L.FL[i] = (L.L[i + 1] + 2 * L.L[i] + L.L[i - 1] + 2) >> 2;
-          L.FT[i] = (L.T[i + 1] + 2 * L.T[i] + L.T[i - 1] + 2) >> 2;
-        }
-      }
-      wave_sync();
-    }
-    const int* RL = filt ? L.FL : L.L;
-    const int* RT = filt ? L.FT : L.T;
-    const int dc = mode == 1 ? intra_dc_value(RL, RT, l2) : 0;
-    const int ang_a = ang.angle[mode], ang_i = ang.inv[mode];
-    for (int i = lane; i < N * N; i += 64) {
-      const int px = i & (N - 1), py = i >> l2;
-      const int p = intra_pred_pixel_ai(RL, RT, l2, mode, ang_a, ang_i, c == 0 && N < 32, dc, px, py);
-      L.pred[i] = (uint8_t)p;
-      L.resid[i] = (int16_t)((int)L.src[(y - by + py) * S + (x - bx + px)] - p);
-    }
-    wave_sync();
+    wave_intra_predict(
+        L.refs, ang, c, x0, y0, l2, mode, g.W, g.H,
+        [&](int xn, int yn) {  // this CTB's reconstruction so far, else the staged borders
+          if (xn >= bx && yn >= by) return L.rec[(yn - by) * S + (xn - bx)];
+          if (yn == by - 1) return L.top[xn - (bx - 1)];
+          return L.left[yn - by];
+        },
+        [&](int px, int py) { return L.src[(y - by + py) * S + (x - bx + px)]; }, L.pred, L.resid);
     const int cb = wave_code_tb<kSdh>(L.resid, L.pred, l2, qpx, true, coefp + (long)y * pw + x, pw,
                                       &L.rec[(y - by) * S + (x - bx)], S, Tm, L.tb, scan_idx_for(true, l2, c, mode));
     if (lane == 0 && cb) atomicOr(&cbfs[k], 1u << c);
@@ -404,35 +273,14 @@ __global__ void __launch_bounds__(256) k_pintra_analysis(FrameSet src, DecisionS
     int16_t* L = R[w][0];
     int16_t* T = R[w][1];
     wave_sync();  // the previous item's reads of this wave's LDS are done
-    if (lane == 0) {
-      const bool a = zscan_available(x, y, x - 1, y - 1, g.W, g.H);
-      av[w][0][0] = av[w][1][0] = a;
-      L[0] = T[0] = a ? S[(long)(y - 1) * g.W + x - 1] : 0;
-    } else if (lane < 33) {
-      const bool al = zscan_available(x, y, x - 1, y + lane - 1, g.W, g.H);
-      av[w][0][lane] = al;
-      L[lane] = al ? S[(long)(y + lane - 1) * g.W + x - 1] : 0;
-      const bool at = zscan_available(x, y, x + lane - 1, y - 1, g.W, g.H);
-      av[w][1][lane] = at;
-      T[lane] = at ? S[(long)(y - 1) * g.W + x + lane - 1] : 0;
-    }
+    if (lane < 33) src_ref_entry(S, g.W, g.H, x, y, lane, L, T, av[w][0], av[w][1]);
     wave_sync();
     if (lane == 0) {
       intra_substitute(L, T, av[w][0], av[w][1], 16);
       dcv[w] = intra_dc_value(L, T, 4);
     }
     wave_sync();
-    if (lane <= 32) {  // [1 2 1] smoothed copies
-      if (lane == 0) {
-        R[w][2][0] = R[w][3][0] = (int16_t)((L[1] + 2 * L[0] + T[1] + 2) >> 2);
-      } else if (lane == 32) {
-        R[w][2][32] = L[32];
-        R[w][3][32] = T[32];
-      } else {
-        R[w][2][lane] = (int16_t)((L[lane + 1] + 2 * L[lane] + L[lane - 1] + 2) >> 2);
-        R[w][3][lane] = (int16_t)((T[lane + 1] + 2 * T[lane] + T[lane - 1] + 2) >> 2);
-      }
-    }
+    if (lane <= 32) intra_smooth_entry<int16_t>(L, T, R[w][2], R[w][3], lane, 32);  // [1 2 1] smoothed copies
     wave_sync();
     int sv[4];
 #pragma unroll
@@ -452,7 +300,7 @@ __global__ void __launch_bounds__(256) k_pintra_analysis(FrameSet src, DecisionS
       int sum = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) sum += wave_satd8x8(sv[k] - pred(mode, k));
-      const unsigned v = ((unsigned)(sum + (mode <= 1 ? pen.mode_dcpl : pen.mode_ang)) << 6) | (unsigned)mode;
+      const unsigned v = intra_cost_key(sum, mode, pen);
       best = v < best ? v : best;
       if (mode >= 2) best_ang = v < best_ang ? v : best_ang;
     };
@@ -498,12 +346,13 @@ __global__ void __launch_bounds__(256) k_pintra_select(DecisionSet dec, Geo g, P
   }
 }
 
-struct PIntraLds {
-  uint8_t pred[256];
-  int16_t resid[256];
-  int V[65];
-  int L[33], T[33], FL[33], FT[33];
-  WaveTbScratch tb;
+// one component's wave state; S = the TB side: 16 (luma) or 8 (chroma)
+template <int S>
+struct PIntraLdsT {
+  uint8_t pred[S * S];
+  int16_t resid[S * S];
+  IntraRefsT<S> refs;
+  WaveTbScratchT<S> tb;
 };
 
 template <bool kSdh>
@@ -514,14 +363,16 @@ __global__ void __launch_bounds__(192) k_pintra_recon(FrameSet src, FrameSet rec
   if ((int)blockIdx.x >= n) return;  // workgroup-uniform
   __shared__ int Tm[32][33];
   __shared__ AngleLds ang;
-  __shared__ PIntraLds W[3];
+  __shared__ PIntraLdsT<16> WY;    // luma
+  __shared__ PIntraLdsT<8> WC[2];  // Cb, Cr
   __shared__ unsigned cbfs;
   tb_load_matrix(Tm);
   ang.load(threadIdx.x, 192);
   __syncthreads();
-  PIntraLds& L = W[c];
-  const int sh = c ? 1 : 0, l2 = 4 - sh, N = 1 << l2, total = 4 * N + 1;
-  const int pw = g.W >> sh;
+  // instantiated for the luma- and the chroma-sized state (each wave runs one: the branch on c
+  // is wave-uniform; both run the same barriers)
+  auto comp = [&](auto& L, const int l2) {
+  const int sh = 4 - l2, pw = g.W >> sh;
   for (int it = blockIdx.x; it < n; it += gridDim.x) {  // workgroup-uniform
     const int cb = pi.pass[(long)q * B * nctu + it], b = cb / nctu, ctu = cb - b * nctu;
     const int x0 = (ctu % g.wc) * 32 + (q & 1) * 16, y0 = (ctu / g.wc) * 32 + (q >> 1) * 16;
@@ -530,62 +381,10 @@ __global__ void __launch_bounds__(192) k_pintra_recon(FrameSet src, FrameSet rec
     const uint8_t* Sp = src.plane(c, b, g);
     uint8_t* Rp = rec.plane(c, b, g);
     if (threadIdx.x == 0) cbfs = 0;
-    // reference samples in canonical order (bottom-left .. corner .. top-right), final
-    // reconstruction read straight from the plane
-    unsigned long long m[2] = {0, 0};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int i = lane + 64 * r;
-      bool a = false;
-      if (i < total) {
-        const int xn = i < 2 * N ? x - 1 : x - 1 + (i - 2 * N), yn = i < 2 * N ? y + 2 * N - 1 - i : y - 1;
-        a = zscan_available(x0, y0, xn << sh, yn << sh, g.W, g.H);
-        L.V[i] = a ? Rp[(long)yn * pw + xn] : 0;
-      }
-      m[r] = __ballot(a);
-    }
-    wave_sync();
-    for (int i = lane; i < total; i += 64) {  // substitution (H.265 8.4.4.2.2): nearest available below
-      int jj = -1;
-      for (int wv = i >> 6; wv >= 0 && jj < 0; --wv) {
-        const unsigned long long mm =
-            (wv == (i >> 6)) ? (m[wv] & (((i & 63) == 63) ? ~0ull : ((2ull << (i & 63)) - 1))) : m[wv];
-        if (mm) jj = wv * 64 + 63 - __clzll(mm);
-      }
-      if (jj < 0)
-        for (int wv = 0; wv < 2 && jj < 0; ++wv)
-          if (m[wv]) jj = wv * 64 + __ffsll(m[wv]) - 1;
-      const int v = jj < 0 ? 128 : L.V[jj];
-      if (i < 2 * N) L.L[2 * N - i] = v;
-      else if (i == 2 * N) L.L[0] = L.T[0] = v;
-      else L.T[i - 2 * N] = v;
-    }
-    wave_sync();
-    const bool filt = c == 0 && intra_filter_refs(l2, mode);
-    if (filt) {
-      for (int i = lane; i <= 2 * N; i += 64) {
-        if (i == 0) {
-          L.FL[0] = L.FT[0] = (L.L[1] + 2 * L.L[0] + L.T[1] + 2) >> 2;
-        } else if (i == 2 * N) {
-          L.FL[i] = L.L[i];
-          L.FT[i] = L.T[i];
-        } else {
-          L.FL[i] = (L.L[i + 1] + 2 * L.L[i] + L.L[i - 1] + 2) >> 2;
-          L.FT[i] = (L.T[i + 1] + 2 * L.T[i] + L.T[i - 1] + 2) >> 2;
-        }
-      }
-      wave_sync();
-    }
-    const int* RL = filt ? L.FL : L.L;
-    const int* RT = filt ? L.FT : L.T;
-    const int dc = mode == 1 ? intra_dc_value(RL, RT, l2) : 0;
-    for (int i = lane; i < N * N; i += 64) {
-      const int px = i & (N - 1), py = i >> l2;
-      const int p = intra_pred_pixel_ai(RL, RT, l2, mode, (int)ang.angle[mode], (int)ang.inv[mode], c == 0, dc, px, py);
-      L.pred[i] = (uint8_t)p;
-      L.resid[i] = (int16_t)((int)Sp[(long)(y + py) * pw + x + px] - p);
-    }
-    wave_sync();
+    // every neighbour is final (acceptance), so it is read straight from the plane
+    wave_intra_predict(
+        L.refs, ang, c, x0, y0, l2, mode, g.W, g.H, [&](int xn, int yn) { return Rp[(long)yn * pw + xn]; },
+        [&](int px, int py) { return Sp[(long)(y + py) * pw + x + px]; }, L.pred, L.resid);
     int16_t* coefp = (c == 0 ? dec.coef_y + b * g.ysz : (c == 1 ? dec.coef_u : dec.coef_v) + b * g.csz);
     const int cbit = wave_code_tb<kSdh>(L.resid, L.pred, l2, c ? chroma_qp(qp, 0) : qp, true, coefp + (long)y * pw + x, pw,
                                         Rp + (long)y * pw + x, pw, Tm, L.tb, scan_idx_for(true, l2, c, mode));
@@ -595,6 +394,9 @@ __global__ void __launch_bounds__(192) k_pintra_recon(FrameSet src, FrameSet rec
       dec.cbf[b * g.usz + (long)((y0 >> 3) + (threadIdx.x >> 1)) * g.w8 + (x0 >> 3) + (threadIdx.x & 1)] = (uint8_t)cbfs;
     __syncthreads();  // cbfs and the LDS are reused by the next item
   }
+  };
+  if (c == 0) comp(WY, 4);
+  else comp(WC[c - 1], 3);
 }
 
 void launch_pintra_decide(FrameSet src, DecisionSet dec, const Geo& g, const RcTables* rc, const PIntraBuffers& pi,

@@ -27,7 +27,6 @@ struct WaveTbScratchT {
   int tmp[N_MAX * 33];
   int coef[N_MAX * N_MAX];
 };
-using WaveTbScratch = WaveTbScratchT<32>;
 
 template <class FX, class FY, class EMIT>
 __device__ __forceinline__ void wave_stage(int log2N, FX X, FY Y, bool split, bool split_x, EMIT emit) {

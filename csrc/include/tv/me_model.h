@@ -106,6 +106,49 @@ TV_HD void me_cand_offset(int k, int& ox, int& oy) {
   oy = k < 3 ? -1 : (k < 5 ? 0 : 1);
 }
 
+// ---- the 21 blocks of a CTB and the bottom-up CU split (I, P and B pictures; CPU == GPU) --
+// block bi: 16 x 8x8 (raster), then 4 x 16x16 (z-order quadrants), then the 32x32
+TV_HD void me_blk_geom(int bi, int& bx, int& by, int& l2) {
+  if (bi < 16) {
+    bx = (bi & 3) * 8;
+    by = (bi >> 2) * 8;
+    l2 = 3;
+  } else if (bi < 20) {
+    bx = ((bi - 16) & 1) * 16;
+    by = ((bi - 16) >> 1) * 16;
+    l2 = 4;
+  } else {
+    bx = by = 0;
+    l2 = 5;
+  }
+}
+// index of the r-th (z-order) 8x8 block of quadrant q
+TV_HD int me_blk8_of(int q, int r) { return (((q >> 1) * 2 + (r >> 1)) << 2) + (q & 1) * 2 + (r & 1); }
+
+// Bottom-up CU split of one CTB from the 21 block costs: a quadrant splits when its four 8x8
+// blocks are strictly cheaper than the 16x16, the CTB stays whole when the 32x32 is no dearer
+// than the quadrants (each CU pays pen_split).  Per 8x8 unit (raster): the CU's log2 size and
+// the index of the block whose mode / motion the unit takes.
+TV_HD void split_ctb(const int* bcost, int pen_split, int sel[16], uint8_t l2[16]) {
+  int sum16 = 0;
+  for (int q = 0; q < 4; ++q) {
+    int sum8 = 0;
+    for (int r = 0; r < 4; ++r) sum8 += bcost[me_blk8_of(q, r)] + pen_split;
+    const bool split = sum8 < bcost[16 + q] + pen_split;
+    sum16 += split ? sum8 : bcost[16 + q] + pen_split;
+    for (int r = 0; r < 4; ++r) {
+      const int ux = (q & 1) * 2 + (r & 1), uy = (q >> 1) * 2 + (r >> 1);
+      sel[uy * 4 + ux] = split ? me_blk8_of(q, r) : 16 + q;
+      l2[uy * 4 + ux] = split ? 3 : 4;
+    }
+  }
+  if (bcost[20] + pen_split <= sum16)
+    for (int k = 0; k < 16; ++k) {
+      sel[k] = 20;
+      l2[k] = 5;
+    }
+}
+
 // ---- SATD sub-pel decision (SeqConfig::subpel_satd, flag bit 256; CPU == GPU) -----------
 // Off by default.  The integer search is unchanged: it gives the integer vector m0 of each
 // of the 21 blocks and cost = SAD + pen.  With the tool on, the half- and quarter-pel rounds
