@@ -805,11 +805,17 @@ struct Tile {
     } else {
       io.sym(y, cdf.y_mode[2], 13);  // Size_Group[BLOCK_16X16] = 2
     }
-    if (directional(y)) {
-      int ad = 3;
-      io.sym(ad, cdf.angle[y - V_PRED], 7);
-      if (ad != 3) throw std::runtime_error("av1 oracle: angle delta outside the encoder subset");
-    }
+    // angle deltas (av1_enc.h "directional intra"): only 90 <= pAngle <= 180 is in the subset
+    auto angle_delta = [&](int m, int delta) {
+      if (IO::kW && !dir_delta_ok(m, delta)) throw std::runtime_error("av1 writer: angle delta outside the encoder subset");
+      int ad = 3 + delta;
+      io.sym(ad, cdf.angle[m - V_PRED], 7);
+      if (!dir_delta_ok(m, ad - 3)) throw std::runtime_error("av1 oracle: angle delta outside the encoder subset");
+      return ad - 3;
+    };
+    int yd = 0, uvd = 0;
+    if (directional(y)) yd = angle_delta(y, IO::kW ? mode_angle_y(mode[b]) : 0);
+    else if (IO::kW && mode_angle_y(mode[b])) throw std::runtime_error("av1 writer: angle delta on a non-directional mode");
     io.sym(uvm, cdf.uv[1][y], 14);  // CfL allowed for 16x16
     int au = 0, av = 0;
     if (uvm == UV_CFL_PRED) {  // read_cfl_alphas: joint sign, then |alpha| - 1 of each nonzero plane
@@ -832,14 +838,14 @@ struct Tile {
         av = sv == 1 ? -(magv + 1) : magv + 1;
       }
     } else if (directional(uvm)) {
-      int ad = 3;
-      io.sym(ad, cdf.angle[uvm - V_PRED], 7);
-      if (ad != 3) throw std::runtime_error("av1 oracle: angle delta outside the encoder subset");
+      uvd = angle_delta(uvm, IO::kW ? mode_angle_uv(mode[b]) : 0);
     }
     ymode[b] = (uint8_t)y;
     if (!IO::kW) {
       mode[b] = pack_mode(0, y, uvm, mode_skip(mode[b]), mode_nz(mode[b]));
       if (uvm == UV_CFL_PRED) mode[b] = with_cfl(mode[b], au, av);
+      else if (uvd) mode[b] = with_angle_uv(mode[b], uvd);
+      if (yd) mode[b] = with_angle_y(mode[b], yd);
     }
   }
 
@@ -1642,8 +1648,9 @@ void predict(const SeqGeo& g, int p, int bx, int by, uint32_t m, uint32_t mvw, c
     for (int i = 0; i < 64; ++i) pred[i] = cfl_pred_px(dc, alpha, ac[i]);
     return;
   }
+  const int delta = p ? mode_angle_uv(m) : mode_angle_y(m);
   for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) pred[i * N + j] = intra_pred_px(mode, e, N, i, j, dc);
+    for (int j = 0; j < N; ++j) pred[i * N + j] = intra_pred_px_ang(mode, delta, e, N, i, j, dc);
 }
 
 }  // namespace
@@ -1916,21 +1923,36 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
         uint32_t mvw = 0;
         // TV_AV1_DBG bit 32: the search also tries D113 / D135 / D157 (conformance tests of
         // the directional predictor; the shipped search leaves them out, av1_enc.h)
-        const int ncand = (dbg & 8) ? 1 : kNumIntraCand + ((dbg & 32) ? 3 : 0);
-        auto cand = [](int k) { return k < kNumIntraCand ? intra_cand(k) : D135_PRED + (k - kNumIntraCand); };
+        // directional intra (kToolDirIntra, av1_enc.h): 34 (mode, delta) candidates in dir_cand
+        // order with CDF-based rates.  TV_AV1_DBG bit 64: those rates over the seven old modes
+        // only (measurement: the rate model without the new angles)
+        const bool dir = (tools & kToolDirIntra) && !(dbg & (8 | 32));
+        const int ncand = dir ? ((dbg & 64) ? kNumIntraCand : kNumDirCand)
+                              : ((dbg & 8) ? 1 : kNumIntraCand + ((dbg & 32) ? 3 : 0));
+        auto cand = [&](int k) {
+          if (dir) return dir_cand_mode(k);
+          return k < kNumIntraCand ? intra_cand(k) : D135_PRED + (k - kNumIntraCand);
+        };
+        auto cand_delta = [&](int k) { return dir ? dir_cand_delta(k) : 0; };
+        const bool kf_ctx = fd.fp.key;
+        // key frames code in raster order: the neighbours' mode words are final (inter frames
+        // take the y_mode table, no neighbour is read)
+        const int ctx_a = kf_ctx && by ? dir_ctx_mode(fd.mode[b - g.bw]) : DC_PRED;
+        const int ctx_l = kf_ctx && bx ? dir_ctx_mode(fd.mode[b - 1]) : DC_PRED;
+        int yd = 0, uvd = 0;
         // chroma decision of an intra block; runs once the block's luma is reconstructed in rec
         // (chroma from luma reads it; the regular modes read the chroma neighbours only)
         auto chroma_search = [&] {
           int best = 1 << 30;
           for (int k = 0; k < ncand; ++k) {
-            const uint32_t m = pack_mode(0, 0, cand(k), 0, 0);
+            const uint32_t m = with_angle_uv(pack_mode(0, 0, cand(k), 0, 0), cand_delta(k));
             int pu[64], pv[64];
             predict(g, 1, bx, by, m, 0, rec, nullptr, pu);
             predict(g, 2, bx, by, m, 0, rec, nullptr, pv);
-            const int cost = satd_block(s[1], pu, 8) + satd_block(s[2], pv, 8) +
-                             ((lam * intra_mode_bits16(cand(k))) >> 8);
+            const int bits = dir ? dir_uv_bits16(ym, cand(k), cand_delta(k)) : intra_mode_bits16(cand(k));
+            const int cost = satd_block(s[1], pu, 8) + satd_block(s[2], pv, 8) + ((lam * bits) >> 8);
             if (cost < best) {
-              best = cost, uvm = cand(k);
+              best = cost, uvm = cand(k), uvd = cand_delta(k);
               std::memcpy(pred[1], pu, sizeof(pu));
               std::memcpy(pred[2], pv, sizeof(pv));
             }
@@ -1953,8 +1975,12 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
               sat[pl][k] = satd_block(s[1 + pl], pc, 8);
             }
           }
-          if (!cfl_decide(a0[0], a0[1], sat[0], sat[1], lam, best, &cfl_u, &cfl_v)) return;
+          if (!(dir ? cfl_decide_bits(a0[0], a0[1], sat[0], sat[1], lam, best, dir_uv_bits16(ym, UV_CFL_PRED, 0), &cfl_u,
+                                      &cfl_v)
+                    : cfl_decide(a0[0], a0[1], sat[0], sat[1], lam, best, &cfl_u, &cfl_v)))
+            return;
           uvm = UV_CFL_PRED;
+          uvd = 0;
           for (int pl = 0; pl < 2; ++pl) {
             const int a = pl ? cfl_v : cfl_u;
             for (int i = 0; i < 64; ++i) pred[1 + pl][i] = cfl_pred_px(dcv[pl], a, ac[i]);
@@ -1963,11 +1989,12 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
         if (fd.fp.key || as_intra) {
           int best = 1 << 30;
           for (int k = 0; k < ncand; ++k) {
-            const uint32_t m = pack_mode(0, cand(k), 0, 0, 0);
+            const uint32_t m = with_angle_y(pack_mode(0, cand(k), 0, 0, 0), cand_delta(k));
             int pr[256];
             predict(g, 0, bx, by, m, 0, rec, nullptr, pr);
-            const int cost = satd_block(s[0], pr, 16) + ((lam * intra_mode_bits16(cand(k))) >> 8);
-            if (cost < best) best = cost, ym = cand(k), std::memcpy(pred[0], pr, sizeof(pr));
+            const int bits = dir ? dir_y_bits16(kf_ctx, ctx_a, ctx_l, cand(k), cand_delta(k)) : intra_mode_bits16(cand(k));
+            const int cost = satd_block(s[0], pr, 16) + ((lam * bits) >> 8);
+            if (cost < best) best = cost, ym = cand(k), yd = cand_delta(k), std::memcpy(pred[0], pr, sizeof(pr));
           }
         } else if (force_mv) {
           inter = 1;
@@ -2035,6 +2062,8 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
         }
         fd.mode[b] = pack_mode(inter, ym, uvm, nz == 0, nz);
         if (uvm == UV_CFL_PRED) fd.mode[b] = with_cfl(fd.mode[b], cfl_u, cfl_v);
+        else if (uvd) fd.mode[b] = with_angle_uv(fd.mode[b], uvd);
+        if (yd) fd.mode[b] = with_angle_y(fd.mode[b], yd);
         fd.mv[b] = inter ? mvw : 0;
     };
     if (fd.fp.key) {  // intra: left / above dependencies (raster order)
@@ -2300,14 +2329,15 @@ const char* tv_av1c_last_error() { return g_codec_err.c_str(); }
 // Dc_Qlookup / Ac_Qlookup (8-bit) of q-index q (dc != 0: the DC table)
 int tv_av1c_qlookup(int q, int dc) { return dc ? dc_q(q) : ac_q(q); }
 
-// Encoder model constants (av1_enc.h) for the GPU engine's host side.  out [6 + kNumLrSets] =
+// Encoder model constants (av1_enc.h) for the GPU engine's host side.  out [7 + kNumLrSets] =
 // kCdefMaskY, kCdefMaskUV, kMvMemoRecordBytes, kIbPasses, kToolIntraInInter, kToolCfl, then
-// the lr_set() values; returns kNumLrSets.
+// the lr_set() values, then kToolDirIntra; returns kNumLrSets.
 int tv_av1c_model_constants(int64_t* out) {
   const int64_t c[6] = {(int64_t)kCdefMaskY, (int64_t)kCdefMaskUV, kMvMemoRecordBytes, kIbPasses, kToolIntraInInter,
                         kToolCfl};
   for (int i = 0; i < 6; ++i) out[i] = c[i];
   for (int k = 0; k < kNumLrSets; ++k) out[6 + k] = lr_set(k);
+  out[6 + kNumLrSets] = kToolDirIntra;
   return kNumLrSets;
 }
 // Per-q-index model values: out [3] = lf_level_for_q, lr_rate_cost, cdef_damping_for_q.
@@ -2396,6 +2426,89 @@ int tv_av1c_cfl_decide(const uint8_t* luma, const uint8_t* su, const uint8_t* sv
     const bool win = cfl_decide(a0[0], a0[1], sat[0], sat[1], lam, best, &au, &av);
     const int32_t r[9] = {den, num[0], num[1], a0[0], a0[1], au, av, win ? 1 : 0, cfl_bits16(au, av)};
     std::memcpy(out, r, sizeof(r));
+  });
+}
+
+// ---- directional intra (av1_enc.h "directional intra"): the model without an encode ----
+namespace {
+// edges [2 * N + 1] = above[0..N-1], left[0..N-1], top-left, as intra_edges leaves them
+void dir_edges(const uint8_t* edges, int N, int have_a, int have_l, IntraEdge& e) {
+  for (int i = 0; i < N; ++i) e.above[i] = edges[i], e.left[i] = edges[N + i];
+  e.tl = edges[2 * N];
+  e.have_a = have_a != 0;
+  e.have_l = have_l != 0;
+}
+}  // namespace
+
+// N x N (8 or 16) prediction of (mode, delta) from the given edges into pred [N * N].
+int tv_av1c_dir_predict(int N, const uint8_t* edges, int have_a, int have_l, int mode, int delta, uint8_t* pred) {
+  return codec_guard([&] {
+    if ((N != 8 && N != 16) || mode < 0 || mode > PAETH_PRED || mode == 3 || mode == 7 || mode == 8 ||
+        !dir_delta_ok(mode, delta))
+      throw std::runtime_error("av1: (mode, delta) outside the encoder subset");
+    IntraEdge e;
+    dir_edges(edges, N, have_a, have_l, e);
+    const int dc = intra_dc(e, N);
+    for (int i = 0; i < N; ++i)
+      for (int j = 0; j < N; ++j) pred[i * N + j] = (uint8_t)intra_pred_px_ang(mode, delta, e, N, i, j, dc);
+  });
+}
+
+// The rate tables (1/16 bit) and the derivative table: kf_y [5][5][13], y_mode [13] (size group
+// 2), uv [13][14], angle [8][7], deriv [88] (Dr_Intra_Derivative by angle, 0 where undefined).
+void tv_av1c_dir_tables(int32_t* kf_y, int32_t* y_mode, int32_t* uv, int32_t* angle, int32_t* deriv) {
+  for (int a = 0; a < 5; ++a)
+    for (int l = 0; l < 5; ++l)
+      for (int m = 0; m < 13; ++m) kf_y[(a * 5 + l) * 13 + m] = tab::kKfYModeBits16[a][l][m];
+  for (int m = 0; m < 13; ++m) y_mode[m] = tab::kYModeBits16[m];
+  for (int y = 0; y < 13; ++y)
+    for (int m = 0; m < 14; ++m) uv[y * 14 + m] = tab::kUvMode1Bits16[y][m];
+  for (int k = 0; k < 8; ++k)
+    for (int d = 0; d < 7; ++d) angle[k * 7 + d] = tab::kAngleDeltaBits16[k][d];
+  for (int a = 0; a < 88; ++a) deriv[a] = 0;
+  for (int k = 0; k < kNumDirCand; ++k) {
+    if (!dir_cand_delta(k) && !(dir_cand_mode(k) >= D135_PRED && dir_cand_mode(k) <= D157_PRED)) continue;
+    const int a = dir_base_angle(dir_cand_mode(k)) + 3 * dir_cand_delta(k);
+    deriv[180 - a] = dr_deriv(180 - a);
+    deriv[a - 90] = dr_deriv(a - 90);
+  }
+}
+
+// The search order: out [34][2] = mode, delta of every candidate.
+void tv_av1c_dir_cands(int32_t* out) {
+  for (int k = 0; k < kNumDirCand; ++k) out[2 * k] = dir_cand_mode(k), out[2 * k + 1] = dir_cand_delta(k);
+}
+
+// The 34-candidate decision (dir_cand order, first strict minimum) of one block.  N = 16: luma,
+// src [256] and edges; rate context kf (key frame), above / left (the neighbours' y modes);
+// src_v / edges_v / ym unused (may be null).  N = 8: chroma, src / edges the U plane's and src_v
+// / edges_v the V plane's, ym the block's chosen y mode; kf / above / left unused.  edges as in
+// tv_av1c_dir_predict.  cost [34]: every candidate's cost; *win: the winner's index.
+int tv_av1c_dir_decide(int N, const uint8_t* src, const uint8_t* src_v, const uint8_t* edges, const uint8_t* edges_v,
+                       int have_a, int have_l, int lam, int kf, int above, int left, int ym, int32_t* cost, int* win) {
+  return codec_guard([&] {
+    if (N != 8 && N != 16) throw std::runtime_error("av1: bad block size");
+    if (N == 8 && (!src_v || !edges_v)) throw std::runtime_error("av1: chroma decision needs both planes");
+    IntraEdge e[2];
+    int s[2][256], dc[2];
+    for (int pl = 0; pl < (N == 8 ? 2 : 1); ++pl) {
+      dir_edges(pl ? edges_v : edges, N, have_a, have_l, e[pl]);
+      dc[pl] = intra_dc(e[pl], N);
+      for (int i = 0; i < N * N; ++i) s[pl][i] = (pl ? src_v : src)[i];
+    }
+    int best = 1 << 30;
+    for (int k = 0; k < kNumDirCand; ++k) {
+      const int m = dir_cand_mode(k), d = dir_cand_delta(k);
+      int c = 0, pr[256];
+      for (int pl = 0; pl < (N == 8 ? 2 : 1); ++pl) {
+        for (int i = 0; i < N; ++i)
+          for (int j = 0; j < N; ++j) pr[i * N + j] = intra_pred_px_ang(m, d, e[pl], N, i, j, dc[pl]);
+        c += satd_block(s[pl], pr, N);
+      }
+      c += (lam * (N == 16 ? dir_y_bits16(kf != 0, above, left, m, d) : dir_uv_bits16(ym, m, d))) >> 8;
+      cost[k] = c;
+      if (c < best) best = c, *win = k;
+    }
   });
 }
 

@@ -12,9 +12,12 @@
 //   k_av1e_intra   one wave per 16x16 block of an anti-diagonal (key frames): the seven
 //                  candidate modes read no above-right samples, so the frame is a plain
 //                  (rows + cols - 1)-step wavefront; 4 luma modes x 16 lanes per pass, all
-//                  7 chroma modes x 8 lanes (U + V 4x4 SATDs) in one pass.  <true>: the opt-in
+//                  7 chroma modes x 8 lanes (U + V 4x4 SATDs) in one pass.  <CFL = true>: the opt-in
 //                  chroma-from-luma instantiation of the block coder (kToolCfl): luma subsample
 //                  from LDS, wave-sum alpha fit, one 24-lane SATD pass over the candidates.
+//                  <DIR = true>: the opt-in directional-intra instantiation (kToolDirIntra): 34
+//                  (mode, angle delta) candidates for luma and for chroma, rates from the default
+//                  CDFs; every angle is strictly between 90 and 180 degrees, so the wavefront holds.
 //   k_av1e_ib_*    opt-in intra blocks of inter frames (tv/av1_enc.h): per-block candidate
 //                  analysis on source neighbours, acceptance + per-pass lists, seven
 //                  list-driven launches of the key-frame block coder.
@@ -743,15 +746,24 @@ __device__ void load_edges(const uint8_t* P, int w, int x, int y, int N, EdgeLds
 // acl[] for the SATD lanes; num / den are wave sums, so the fitted alphas are wave-uniform;
 // one extra SATD pass covers the 2 planes x 3 candidates (24 lanes, one 4x4 each, summed over
 // each quad) and cfl_decide compares the result with the best regular mode.
-template <bool CFL>
+// DIR (kToolDirIntra, tv/av1_enc.h "directional intra"): both searches run over the 34 dir_cand
+// candidates with CDF rates.  The seven intra_cand modes keep their passes; the 27 angled
+// candidates follow, 4 (luma) / 8 (chroma) per pass in the same lane layout, each lane group
+// looking up its candidate's (dx, dy) and predicting with intra_dir_px alone (every such angle is
+// strictly between 90 and 180 degrees).  kf (a literal in each kernel) selects the rate context:
+// key-frame blocks read the y modes of their above / left neighbours from mode[], which the
+// launches of earlier anti-diagonals on the same stream wrote; the intra blocks of inter frames
+// take the y_mode table and read no neighbour.
+template <bool CFL, bool DIR>
 __device__ __forceinline__ void intra_code_block(const Planes3& src, const Planes3W& rec, uint32_t* __restrict__ mode,
                                                  uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
                                                  int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
-                                                 int qidx, int b, int bx, int by) {
+                                                 int qidx, int b, int bx, int by, const bool kf) {
+  constexpr int kCflCost = DIR ? 40 : 8;  // cost[] slots of the CfL candidates
   __shared__ EdgeLds E[2];
   __shared__ uint8_t sblk[256];
   __shared__ uint8_t sc[2][64];
-  __shared__ int cost[16];
+  __shared__ int cost[DIR ? 48 : 16];
   __shared__ int16_t res[256], ta[256], tb[256];
   __shared__ int32_t ti[256];
   __shared__ int predc[256];
@@ -768,6 +780,12 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
   load_edges(RY, W, x0, y0, 16, E[0]);
   // ---- luma: kNumIntraCand candidates, 4 per pass (16 lanes = 16 4x4 SATDs each)
   const int grp = lane >> 4, b4 = lane & 15, px = (b4 & 3) * 4, py = (b4 >> 2) * 4;
+  int ca = DC_PRED, cl = DC_PRED;  // DIR, key frames: the neighbours' y modes (rate context)
+  if (DIR && kf) {
+    const long o = (long)b * bw * (H >> 4) + by * bw + bx;
+    if (by) ca = dir_ctx_mode(mode[o - bw]);
+    if (bx) cl = dir_ctx_mode(mode[o - 1]);
+  }
   for (int pass = 0; pass < (kNumIntraCand + 3) / 4; ++pass) {
     const int ci = pass * 4 + grp;
     const int m = intra_cand(ci < kNumIntraCand ? ci : 0);
@@ -778,18 +796,42 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
       for (int j = 0; j < 4; ++j)
         d[i * 4 + j] = (int)sblk[(py + i) * 16 + px + j] - intra_pred_px(m, E[0].e, 16, py + i, px + j, E[0].dc);
     const int sat = row16_sum(satd4(d));
-    if (b4 == 0 && ci < kNumIntraCand) cost[ci] = sat + ((lam * intra_mode_bits16(m)) >> 8);
+    if (b4 == 0 && ci < kNumIntraCand)
+      cost[ci] = sat + ((lam * (DIR ? dir_y_bits16(kf, ca, cl, m, 0) : intra_mode_bits16(m))) >> 8);
+  }
+  int yd = 0, uvd = 0;
+  if constexpr (DIR) {
+    for (int pass = 0; pass < (kNumDirCand - kNumIntraCand + 3) / 4; ++pass) {
+      const int ci = kNumIntraCand + pass * 4 + grp, k = ci < kNumDirCand ? ci : kNumIntraCand;
+      const int m = dir_cand_mode(k), dl = dir_cand_delta(k), a = dir_base_angle(m) + 3 * dl;
+      const int dx = dr_deriv(180 - a), dy = dr_deriv(a - 90);
+      int d[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          d[i * 4 + j] = (int)sblk[(py + i) * 16 + px + j] - intra_dir_px(E[0].e, py + i, px + j, dx, dy);
+      const int sat = row16_sum(satd4(d));
+      if (b4 == 0 && ci < kNumDirCand) cost[ci] = sat + ((lam * dir_y_bits16(kf, ca, cl, m, dl)) >> 8);
+    }
   }
   __syncthreads();
   int ym = intra_cand(0);
-  {
+  if constexpr (DIR) {
+    int bc = cost[0], bk = 0;
+    for (int k = 1; k < kNumDirCand; ++k)
+      if (cost[k] < bc) bc = cost[k], bk = k;
+    ym = dir_cand_mode(bk), yd = dir_cand_delta(bk);
+  } else {
     int bc = cost[0];
     for (int k = 1; k < kNumIntraCand; ++k)
       if (cost[k] < bc) bc = cost[k], ym = intra_cand(k);
   }
   __syncthreads();
   for (int i = lane; i < 256; i += 64) {
-    const int p = intra_pred_px(ym, E[0].e, 16, i >> 4, i & 15, E[0].dc);
+    int p;
+    if constexpr (DIR) p = intra_pred_px_ang(ym, yd, E[0].e, 16, i >> 4, i & 15, E[0].dc);
+    else p = intra_pred_px(ym, E[0].e, 16, i >> 4, i & 15, E[0].dc);
     predc[i] = p;
     res[i] = (int16_t)((int)sblk[i] - p);
   }
@@ -824,12 +866,36 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
       for (int j = 0; j < 4; ++j)
         d[i * 4 + j] = (int)sc[pl][(qy + i) * 8 + qx + j] - intra_pred_px(m, E[pl].e, 8, qy + i, qx + j, E[pl].dc);
     const int sat = row8_sum(satd4(d));
-    if (q == 0 && ci < kNumIntraCand) cost[ci] = sat + ((lam * intra_mode_bits16(m)) >> 8);
+    if (q == 0 && ci < kNumIntraCand)
+      cost[ci] = sat + ((lam * (DIR ? dir_uv_bits16(ym, m, 0) : intra_mode_bits16(m))) >> 8);
+  }
+  if constexpr (DIR) {
+    for (int pass = 0; pass < (kNumDirCand - kNumIntraCand + 7) / 8; ++pass) {
+      const int ci = kNumIntraCand + pass * 8 + (lane >> 3), k = ci < kNumDirCand ? ci : kNumIntraCand;
+      const int q = lane & 7, pl = q >> 2, qb = q & 3, qx = (qb & 1) * 4, qy = (qb >> 1) * 4;
+      const int m = dir_cand_mode(k), dl = dir_cand_delta(k), a = dir_base_angle(m) + 3 * dl;
+      const int dx = dr_deriv(180 - a), dy = dr_deriv(a - 90);
+      int d[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          d[i * 4 + j] = (int)sc[pl][(qy + i) * 8 + qx + j] - intra_dir_px(E[pl].e, qy + i, qx + j, dx, dy);
+      const int sat = row8_sum(satd4(d));
+      if (q == 0 && ci < kNumDirCand) cost[ci] = sat + ((lam * dir_uv_bits16(ym, m, dl)) >> 8);
+    }
   }
   __syncthreads();
   int uvm = intra_cand(0), bc = cost[0];
-  for (int k = 1; k < kNumIntraCand; ++k)
-    if (cost[k] < bc) bc = cost[k], uvm = intra_cand(k);
+  if constexpr (DIR) {
+    int bk = 0;
+    for (int k = 1; k < kNumDirCand; ++k)
+      if (cost[k] < bc) bc = cost[k], bk = k;
+    uvm = dir_cand_mode(bk), uvd = dir_cand_delta(bk);
+  } else {
+    for (int k = 1; k < kNumIntraCand; ++k)
+      if (cost[k] < bc) bc = cost[k], uvm = intra_cand(k);
+  }
   int au = 0, av = 0;
   if constexpr (CFL) {
     const int a0u = cfl_fit(wave_sum(ac * ((int)sc[0][lane] - E[0].dc)), den);
@@ -851,15 +917,22 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
     }
     sat += dpp::mov<dpp::kQuadXor1>(sat);
     sat += dpp::mov<dpp::kQuadXor2>(sat);
-    if (lane < 24 && qb == 0) cost[8 + pl * 3 + k] = sat;
+    if (lane < 24 && qb == 0) cost[kCflCost + pl * 3 + k] = sat;
     __syncthreads();
-    if (cfl_decide(a0u, a0v, &cost[8], &cost[11], lam, bc, &au, &av)) uvm = UV_CFL_PRED;
+    if constexpr (DIR) {
+      if (cfl_decide_bits(a0u, a0v, &cost[kCflCost], &cost[kCflCost + 3], lam, bc, dir_uv_bits16(ym, UV_CFL_PRED, 0), &au,
+                          &av))
+        uvm = UV_CFL_PRED, uvd = 0;
+    } else {
+      if (cfl_decide(a0u, a0v, &cost[kCflCost], &cost[kCflCost + 3], lam, bc, &au, &av)) uvm = UV_CFL_PRED;
+    }
   }
   const int txt = uv_txtype(uvm);
   for (int pl = 0; pl < 2; ++pl) {
     __syncthreads();
     int p;
     if (CFL && uvm == UV_CFL_PRED) p = cfl_pred_px(E[pl].dc, pl ? av : au, ac);
+    else if (DIR) p = intra_pred_px_ang(uvm, uvd, E[pl].e, 8, lane >> 3, lane & 7, E[pl].dc);
     else p = intra_pred_px(uvm, E[pl].e, 8, lane >> 3, lane & 7, E[pl].dc);
     predc[lane] = p;
     res[lane] = (int16_t)((int)sc[pl][lane] - p);
@@ -872,18 +945,20 @@ __device__ __forceinline__ void intra_code_block(const Planes3& src, const Plane
   if (lane == 0) {
     uint32_t m = pack_mode(0, ym, uvm, nz == 0, nz);
     if (CFL && uvm == UV_CFL_PRED) m = with_cfl(m, au, av);
+    else if (DIR && uvd) m = with_angle_uv(m, uvd);
+    if (DIR && yd) m = with_angle_y(m, yd);
     mode[bo] = m;
     mvout[bo] = 0;
   }
 }
 
-template <bool CFL>
+template <bool CFL, bool DIR>
 __global__ void __launch_bounds__(64) k_av1e_intra(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
                                                    uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
                                                    int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
                                                    const int* __restrict__ qarr, int diag, int bx_lo) {
   const int b = blockIdx.y, bx = bx_lo + blockIdx.x;
-  intra_code_block<CFL>(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, bx, diag - bx);
+  intra_code_block<CFL, DIR>(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, bx, diag - bx, true);
 }
 
 // ================================================== intra blocks in inter frames =========
@@ -956,7 +1031,7 @@ __global__ void k_av1e_ib_select(const uint8_t* __restrict__ cand, uint8_t* __re
   }
 }
 
-template <bool CFL>
+template <bool CFL, bool DIR>
 __global__ void __launch_bounds__(64) k_av1e_ib_recon(Planes3 src, Planes3W rec, uint32_t* __restrict__ mode,
                                                       uint32_t* __restrict__ mvout, int16_t* __restrict__ ly,
                                                       int16_t* __restrict__ lu, int16_t* __restrict__ lv, int W, int H,
@@ -965,7 +1040,7 @@ __global__ void __launch_bounds__(64) k_av1e_ib_recon(Planes3 src, Planes3W rec,
   const int b = blockIdx.y, bw = W >> 4, nb = bw * (H >> 4), slot = b * kIbPasses + pass;
   if ((int)blockIdx.x >= min(cnt[slot], nb)) return;  // wave-uniform: beyond the pass's count
   const int blk = (int)list[(long)slot * nb + blockIdx.x];
-  intra_code_block<CFL>(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, blk % bw, blk / bw);
+  intra_code_block<CFL, DIR>(src, rec, mode, mvout, ly, lu, lv, W, H, qarr[b], b, blk % bw, blk / bw, false);
 }
 
 // ================================================================= loop-filter info ======
@@ -1280,7 +1355,8 @@ int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const
 // o* / mode / mv / l* are the frame's reconstruction and decisions (accepted blocks are
 // overwritten); icost [B][nb] from tv_av1e_inter; scratch cand [B][nb] bytes, cnt
 // [B][7] ints, list [B][7][nb] words; ib [B][nb]: bit 0 candidate, bit 1 accepted.
-// tools: the coding-tools word (kToolCfl: the accepted blocks also try chroma from luma).
+// tools: the coding-tools word (kToolCfl: the accepted blocks also try chroma from luma;
+// kToolDirIntra: their mode searches run over the 34 directional-intra candidates).
 int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
                     uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, const int* icost,
                     uint8_t* cand, uint8_t* ib, int* cnt, uint32_t* list, int W, int H, int B, const int* qarr,
@@ -1293,7 +1369,9 @@ int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uin
   k_av1e_ib_select<<<dim3((nb + 255) / 256, B), 256, 0, st>>>(cand, ib, cnt, list, W, H);
   // a 4x4-block tile has at most 4 blocks of one pass (lx + ly = 3), whole or cut by the frame edge
   const int gmax = (((W >> 4) + 3) >> 2) * (((H >> 4) + 3) >> 2) * 4;
-  const auto recon = (tools & kToolCfl) ? k_av1e_ib_recon<true> : k_av1e_ib_recon<false>;
+  const bool cfl = tools & kToolCfl;
+  const auto recon = (tools & kToolDirIntra) ? (cfl ? k_av1e_ib_recon<true, true> : k_av1e_ib_recon<false, true>)
+                                             : (cfl ? k_av1e_ib_recon<true, false> : k_av1e_ib_recon<false, false>);
   for (int pass = 0; pass < kIbPasses; ++pass)
     recon<<<dim3(gmax, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov}, mode, mv, ly, lu, lv, W, H, qarr,
                                         cnt, list, pass);
@@ -1301,13 +1379,16 @@ int tv_av1e_iblocks(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uin
 }
 
 // Key frame of B segments: one launch per anti-diagonal of the 16x16 block grid.
-// tools: the coding-tools word (kToolCfl: every block also tries chroma from luma).
+// tools: the coding-tools word (kToolCfl: every block also tries chroma from luma; kToolDirIntra:
+// the mode searches run over the 34 directional-intra candidates with CDF rates).
 int tv_av1e_intra(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, uint8_t* oy, uint8_t* ou, uint8_t* ov,
                   uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu, int16_t* lv, int W, int H, int B,
                   const int* qarr, int tools, void* stream) {
   if (bad(W, H, B, 1, "av1e_intra") || ensure_tables()) return -1;
   const int bw = W >> 4, bh = H >> 4;
-  const auto intra = (tools & kToolCfl) ? k_av1e_intra<true> : k_av1e_intra<false>;
+  const bool cfl = tools & kToolCfl;
+  const auto intra = (tools & kToolDirIntra) ? (cfl ? k_av1e_intra<true, true> : k_av1e_intra<false, true>)
+                                             : (cfl ? k_av1e_intra<true, false> : k_av1e_intra<false, false>);
   for (int d = 0; d < bw + bh - 1; ++d) {
     const int lo = d - (bh - 1) > 0 ? d - (bh - 1) : 0, hi = d < bw - 1 ? d : bw - 1;
     intra<<<dim3(hi - lo + 1, B), 64, 0, (hipStream_t)stream>>>(Planes3{sy, su, sv}, Planes3W{oy, ou, ov}, mode, mv,

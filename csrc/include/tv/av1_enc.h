@@ -12,7 +12,12 @@
 //     so the I-frame wavefront is a plain diagonal; angle delta 0; intra edge filter / filter
 //     intra / palette off; opt-in (kToolCfl, off by default): chroma from luma as an eighth
 //     chroma mode of every intra block ("chroma from luma" below), which reads only the
-//     block's own reconstructed luma, so the wavefront is unchanged;
+//     block's own reconstructed luma, so the wavefront is unchanged; opt-in (kToolDirIntra,
+//     off by default): every directional angle strictly between 90 and 180 degrees (V / H /
+//     D113 / D135 / D157 with angle deltas, 34 (mode, delta) candidates for luma and for
+//     chroma) searched with mode rates read from the default CDFs ("directional intra"
+//     below); those angles read nothing right of above[N-1] or below left[N-1], so the
+//     wavefront is unchanged;
 //   * inter frames: one reference (LAST = previous frame), quarter-pel motion, EIGHTTAP
 //     (regular) filters; the NEWMV / NEARESTMV / NEARMV / GLOBALMV choice is made by the
 //     syntax writer from the spatial MV stack (the mode does not change the reconstruction);
@@ -46,7 +51,7 @@ enum : int { NEARESTMV = 13, NEARMV = 14, GLOBALMV = 15, NEWMV = 16 };
 // decodes them bit-exactly) but the SATD-driven search picked them where they cost more than
 // they saved: key-frame-only clips at QP 27 +1.0 % bytes at -0.09 dB even with a 10-bit mode
 // penalty (profiles/README.md, round 4), so the search keeps the seven non-directional-delta
-// modes until it gets a rate-aware decision.
+// modes; the opt-in rate-aware decision is "directional intra" below (kToolDirIntra).
 constexpr int kNumIntraCand = 7;
 TV_HD int intra_cand(int i) {
   constexpr int8_t m[kNumIntraCand] = {DC_PRED, V_PRED, H_PRED, SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, PAETH_PRED};
@@ -673,6 +678,108 @@ TV_HD bool cfl_decide(int a0u, int a0v, const int* satu3, const int* satv3, int 
   if (!*au && !*av) return false;
   return su + sv + ((lam * cfl_bits16(*au, *av)) >> 8) < best;
 }
+// the same with the mode term given (kToolDirIntra: uv[y mode][13] of the default CDFs)
+TV_HD bool cfl_decide_bits(int a0u, int a0v, const int* satu3, const int* satv3, int lam, int best, int mode_bits16,
+                           int* au, int* av) {
+  int su = 0, sv = 0;
+  *au = cfl_pick(a0u, satu3, lam, &su);
+  *av = cfl_pick(a0v, satv3, lam, &sv);
+  if (!*au && !*av) return false;
+  return su + sv + ((lam * (mode_bits16 + cfl_alpha_bits16(*au) + cfl_alpha_bits16(*av))) >> 8) < best;
+}
+
+// ------------------------------------------------------------- directional intra -------
+// Opt-in tool (kToolDirIntra, off by default): the luma and the chroma mode search of every
+// intra block (key frames and the accepted intra blocks of inter frames) run over 34 (mode,
+// angle delta) candidates with rates read from the default CDFs.  With the tool off every
+// stream, mode word and kernel instruction is what it was.
+//   angles      pAngle = base + 3 * delta, delta in -3..3, only 90 < pAngle < 180 (plus plain V
+//               and H): V_PRED +1..+3 (93, 96, 99), H_PRED -1..-3 (177, 174, 171), D113 / D135 /
+//               D157 -3..+3 (104..122, 126..144, 148..166).  D45 / D67 / D203, V with delta < 0
+//               and H with delta > 0 are never produced; the writer and the oracle refuse them
+//               (dir_delta_ok).  Such an angle reads above[-1 .. N-1] and left[-1 .. N-1] only
+//               (intra_dir_px: base >= -1 and base + 1 <= N - 1 for every (i, j), N = 8 and 16,
+//               tests/test_av1_dir_intra.py): nothing right of above[N-1] or below left[N-1],
+//               so the key-frame anti-diagonal wavefront and the pass argument of "intra blocks
+//               in inter frames" above hold unchanged.  The intra edge filter and upsampling
+//               stay off in the sequence header, so intra_dir_px is the whole predictor:
+//               dx = Dr_Intra_Derivative[180 - pAngle], dy = [pAngle - 90] (dr_deriv).
+//   rates       1/16 bit, bits16(p) = round(16 * log2(32768 / p)) of the default CDFs
+//               (tv/av1_tables.h k*Bits16, generated with the CDFs): luma cost = SATD16 + ((lam *
+//               (ymode_bits + angle_bits)) >> 8), ymode_bits from kf_y[ctx(above)][ctx(left)] in
+//               key frames (a missing neighbour counts as DC_PRED; intra_mode_ctx is the
+//               writer's context map) and from y_mode[size group 2] in inter frames; angle_bits
+//               = angle[mode][delta] of a directional mode, else 0.  Chroma cost = SATD8(U) +
+//               SATD8(V) + ((lam * (uv[chosen y mode][uv mode] + angle_bits)) >> 8), the
+//               CfL-allowed table.  With kToolCfl also on, CfL's mode term is uv[y mode][13]
+//               instead of kCflModeBits16; its alpha terms and "strictly cheaper" rule stay.
+//               All 34 candidates use these rates, the seven of intra_cand included.
+//   search      exhaustive in the order of dir_cand: the seven intra_cand modes; V +1 +2 +3; H
+//               -1 -2 -3; D135, D113, D157 each with deltas 0 -1 +1 -2 +2 -3 +3; the first strict
+//               minimum wins.  Luma and chroma use the same list; chroma chooses independently.
+//               The intra-in-inter analysis (ib_best_cost) keeps its seven modes and flat rates,
+//               so the candidate and accepted maps do not depend on the tool.
+//   mode word   luma delta as 3-bit two's complement in bits 27-29; chroma delta likewise in
+//               bits 15-17 when the uv mode is directional (the field is the CfL alphas' only
+//               when the uv mode is 13); delta 0 is stored as 0, so tool-off words are unchanged.
+// The derivative table is written from memory; tests/test_av1_dir_intra.py compares it with
+// the bundled decoder library's copy and dav1d decodes the streams sample for sample.
+constexpr int kToolDirIntra = 4;  // bit of the encoders' tools word
+constexpr int kNumDirCand = 34;
+TV_HD bool mode_directional(int m) { return m >= V_PRED && m <= 8; }
+// Dr_Intra_Derivative at the angles 3, 6, 9, 14, .. 87, indexed by angle / 3
+TV_HD int dr_deriv(int a) {
+  constexpr uint16_t t[30] = {0,  1023, 547, 372, 273, 215, 178, 151, 132, 116, 102, 0,  90, 80, 71,
+                              64, 57,   51,  45,  40,  35,  31,  27,  23,  19,  15,  0,  11, 7,  3};
+  return t[a / 3];
+}
+TV_HD int dir_base_angle(int m) {
+  return m == V_PRED ? 90 : (m == H_PRED ? 180 : (m == D135_PRED ? 135 : (m == D113_PRED ? 113 : 157)));
+}
+// (mode, delta) pairs of the encoder subset: 90 <= pAngle <= 180, the ends only as plain V / H
+TV_HD bool dir_delta_ok(int m, int delta) {
+  if (delta < -3 || delta > 3) return false;
+  if (!mode_directional(m)) return delta == 0;
+  if (m == V_PRED) return delta >= 0;
+  if (m == H_PRED) return delta <= 0;
+  return m == D135_PRED || m == D113_PRED || m == D157_PRED;
+}
+// candidate k of the search: mode, angle delta
+TV_HD int dir_cand_mode(int k) {
+  constexpr int8_t m[3] = {D135_PRED, D113_PRED, D157_PRED};
+  return k < kNumIntraCand ? intra_cand(k) : (k < 10 ? V_PRED : (k < 13 ? H_PRED : m[(k - 13) / 7]));
+}
+TV_HD int dir_cand_delta(int k) {
+  if (k < kNumIntraCand) return 0;
+  if (k < 10) return k - 6;
+  if (k < 13) return 9 - k;
+  const int r = (k - 13) % 7;  // 0 -1 +1 -2 +2 -3 +3
+  return (r & 1) ? -((r + 1) >> 1) : (r >> 1);
+}
+TV_HD uint32_t with_angle_y(uint32_t m, int delta) { return (m & ~(7u << 27)) | ((uint32_t)(delta & 7) << 27); }
+TV_HD uint32_t with_angle_uv(uint32_t m, int delta) { return (m & ~(7u << 15)) | ((uint32_t)(delta & 7) << 15); }
+TV_HD int mode_angle_y(uint32_t m) { return (int)(((m >> 27) & 7) ^ 4) - 4; }
+TV_HD int mode_angle_uv(uint32_t m) { return mode_directional(mode_uv(m)) ? (int)(((m >> 15) & 7) ^ 4) - 4 : 0; }
+// predicted sample of (mode, delta); delta 0 is intra_pred_px
+TV_HD int intra_pred_px_ang(int mode, int delta, const IntraEdge& e, int N, int i, int j, int dc) {
+  if (!delta) return intra_pred_px(mode, e, N, i, j, dc);
+  const int a = dir_base_angle(mode) + 3 * delta;
+  return intra_dir_px(e, i, j, dr_deriv(180 - a), dr_deriv(a - 90));
+}
+// rate terms (1/16 bit).  Intra_Mode_Context of a neighbour's y mode (the writer's kIntraModeCtx)
+TV_HD int intra_mode_ctx(int m) {
+  constexpr int8_t c[13] = {0, 1, 2, 3, 4, 4, 4, 4, 3, 0, 1, 2, 0};
+  return c[m];
+}
+TV_HD int dir_angle_bits16(int m, int delta) { return mode_directional(m) ? tab::kAngleDeltaBits16[m - V_PRED][delta + 3] : 0; }
+// kf: key frame, above / left = the neighbours' y modes (DC_PRED where missing)
+TV_HD int dir_y_bits16(bool kf, int above, int left, int m, int delta) {
+  const int mb = kf ? tab::kKfYModeBits16[intra_mode_ctx(above)][intra_mode_ctx(left)][m] : tab::kYModeBits16[m];
+  return mb + dir_angle_bits16(m, delta);
+}
+TV_HD int dir_uv_bits16(int ym, int uvm, int delta) { return tab::kUvMode1Bits16[ym][uvm] + dir_angle_bits16(uvm, delta); }
+// y mode of a neighbour's mode word for the key-frame context
+TV_HD int dir_ctx_mode(uint32_t m) { return mode_inter(m) ? DC_PRED : mode_y(m); }
 
 // deblocking info word for a 4x4 unit (av1_defs.h layout): tx = block = 16 << bsz luma,
 // 8 << bsz chroma

@@ -91,6 +91,10 @@ CORE = {
                                   i32p, u8p]),
     "tv_av1c_ib_accept": (i, [u8p, i, i, u8p]),
     "tv_av1c_cfl_decide": (i, [u8p, u8p, u8p, i, i, i, i, i32p]),
+    "tv_av1c_dir_predict": (i, [i, u8p, i, i, i, i, u8p]),
+    "tv_av1c_dir_tables": (None, [i32p] * 5),
+    "tv_av1c_dir_cands": (None, [i32p]),
+    "tv_av1c_dir_decide": (i, [i, u8p, u8p, u8p, u8p, i, i, i, i, i, i, i, i32p, i32p]),
     "tv_av1c_decode": (i, [u8p, sz, i, u8p, i32p, i32p]),
     "tv_av1c_probe": (i, [u8p, sz, i32p, i32p]),
     "tv_av1c_state_new": (vp, []),

@@ -7,8 +7,10 @@ current HIP stream:
     key frame   k_av1e_intra (anti-diagonal wavefront of 16x16 blocks)
     P frame     k_av1e_inter (full-pel +-16 LDS search, quarter-pel refine, recon)
                 [intra_in_inter: k_av1e_ib_analyse -> k_av1e_ib_select -> 7 x k_av1e_ib_recon]
-                [cfl: the <true> instantiations of k_av1e_intra / k_av1e_ib_recon, whose block
+                [cfl: the <CFL = true> instantiations of k_av1e_intra / k_av1e_ib_recon, whose block
                  coder also tries chroma from luma]
+                [dir_intra: their <DIR = true> instantiations, whose mode searches run over 34
+                 (mode, angle delta) candidates with rates from the default CDFs]
     both        k_av1e_lfinfo -> k_deblock (Y, U, V) -> k_cdef_dir -> k_av1e_cdef_skip ->
                 k_cdef_search (Y, U, V) -> k_av1e_cdef_choose -> k_cdef_apply -> next reference
 
@@ -49,6 +51,7 @@ def _model():
     q = np.zeros((256, 3), np.int64)
     for i in range(256):
         lib.tv_av1c_model_q(i, q[i].ctypes.data_as(C.POINTER(C.c_int64)))
+    assert c[6 + nsets] == av1m.TOOL_DIR_INTRA  # appended after the lr sets (kToolDirIntra)
     return list(c[:6]) + [tuple(c[6:6 + nsets])], q
 
 
@@ -139,17 +142,21 @@ class Av1GpuEngine:
 
     def __init__(self, width: int, height: int, batch: int, qindex: int = 100, device: int = 0,
                  threads: int | None = None, cascade: bool = True, intra_in_inter: bool = False,
-                 cfl: bool = False):
+                 cfl: bool = False, dir_intra: bool = False):
         """`intra_in_inter` (off by default): 16x16 blocks of inter frames may be coded as intra
         blocks (av1_enc.h "intra blocks in inter frames"; k_av1e_ib_*), as the golden encoder
         does with the same flag.  `cfl` (off by default): intra blocks may predict chroma from
-        their reconstructed luma (av1_enc.h "chroma from luma"; k_av1e_intra<true> /
-        k_av1e_ib_recon<true>)."""
+        their reconstructed luma (av1_enc.h "chroma from luma"; the CFL instantiations of
+        k_av1e_intra / k_av1e_ib_recon).  `dir_intra` (off by default): the intra mode searches run
+        over every directional angle strictly between 90 and 180 degrees with CDF-based rates
+        (av1_enc.h "directional intra"; the DIR instantiations of the same kernels)."""
         import torch
 
         self.intra_in_inter = bool(intra_in_inter)
         self.cfl = bool(cfl)
-        self.tools = TOOL_CFL if self.cfl else 0  # the kernels' tools word (intra_in_inter is a launch of its own)
+        self.dir_intra = bool(dir_intra)
+        # the kernels' tools word (intra_in_inter is a launch of its own)
+        self.tools = (TOOL_CFL if self.cfl else 0) | (av1m.TOOL_DIR_INTRA if self.dir_intra else 0)
         self.cascade = bool(cascade)  # constant q: the low-delay q cascade (av1.cascade_qmap)
         self.torch = torch
         self.w, self.h, self.B, self.q = width, height, batch, int(qindex)

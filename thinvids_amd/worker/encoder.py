@@ -58,13 +58,15 @@ class EncodeSpec:
     sign_hiding: bool = False  # sign data hiding: one sign per coefficient group in the parity (tv/sdh.h)
     intra_in_inter: bool = False  # AV1: 16x16 intra blocks in inter frames (tv/av1_enc.h)
     cfl: bool = False  # AV1: chroma from luma in intra blocks (tv/av1_enc.h)
+    dir_intra: bool = False  # AV1: directional intra angles with CDF-based mode rates (tv/av1_enc.h)
     # where the WPP substreams are CABAC-coded ("auto" / "gpu" / "host"): the same bytes, so
     # not a coding tool (not in tools() / the checkpoint fingerprint), but its own engine
     entropy: str = "auto"
 
     def engine_key(self):
         if self.codec == "av1":
-            return ("av1", self.width, self.height, self.av1_qindex(), self.cascade, self.intra_in_inter, self.cfl)
+            return ("av1", self.width, self.height, self.av1_qindex(), self.cascade, self.intra_in_inter, self.cfl,
+                    self.dir_intra)
         return (self.width, self.height, self.qp, self.gop, self.search_range, self.deblock, self.sao, self.seed,
                 self.crf, self.hevc_bframes(), self.wpp, self.rqt, self.pintra, self.cascade, self.rdoq, self.entropy, self.subpel_satd,
                 self.sign_hiding)
@@ -80,6 +82,8 @@ class EncodeSpec:
             t["intra_in_inter"] = True
         if self.cfl and self.codec == "av1":
             t["cfl"] = True
+        if self.dir_intra and self.codec == "av1":
+            t["dir_intra"] = True
         return t
 
     def hevc_bframes(self) -> int:
@@ -210,7 +214,8 @@ class EngineCache:
             from ..models.av1_engine import Av1GpuEngine
 
             eng = Av1GpuEngine(spec.width, spec.height, batch=batch, qindex=spec.av1_qindex(), device=self.device,
-                               cascade=spec.cascade, intra_in_inter=spec.intra_in_inter, cfl=spec.cfl)
+                               cascade=spec.cascade, intra_in_inter=spec.intra_in_inter, cfl=spec.cfl,
+                               dir_intra=spec.dir_intra)
             eng.batch = eng.B
             return eng
         return GpuEngine(spec.width, spec.height, qp=spec.qp, batch=batch, gop=spec.gop, search_range=spec.search_range,
@@ -382,7 +387,8 @@ def _encode_cpu(frames, spec: EncodeSpec, st: PartStats | None, fq=None) -> byte
         for a in range(0, len(frames), spec.gop):
             qm = None if fq is None else [av1.qindex_for_hevc_qp(int(x)) for x in fq[a:a + spec.gop]]
             r = av1.golden_encode(frames[a:a + spec.gop], spec.width, spec.height, spec.av1_qindex(), qmap=qm,
-                                  cascade=spec.cascade, intra_in_inter=spec.intra_in_inter, cfl=spec.cfl)
+                                  cascade=spec.cascade, intra_in_inter=spec.intra_in_inter, cfl=spec.cfl,
+                                  dir_intra=spec.dir_intra)
             bs += r.stream
             for f in r.recon:
                 recons.append((f[:W * H].reshape(H, W), f[W * H:W * H * 5 // 4].reshape(H // 2, W // 2),

@@ -1,14 +1,17 @@
-"""AV1 engine speed, bytes and PSNR with chroma from luma (cfl, tv/av1_enc.h) off and on.
+"""AV1 engine speed, bytes and PSNR with an opt-in intra tool off and on: chroma from luma (--name
+cfl, the default) or directional intra (--name dir_intra); both in tv/av1_enc.h.
 
     python tools/av1_cfl_speed.py [--res 1920x1080] [--qindex 100] [--gop 64] [--batch 8] [--textured]
                                   [--intra-in-inter] [--rounds 3] [--steps 2] [--warmup 1] [--out FILE]
     python tools/av1_cfl_speed.py --gop 2            # key-frame heavy: every second frame is a key frame
+    python tools/av1_cfl_speed.py --name dir_intra   # the same for directional intra
     python tools/av1_cfl_speed.py --tool on --once   # one untimed step of one engine, for a kernel profiler
 
 Both engines (tool off, tool on) live in this one process and take turns, off / on / off / on ...,
 so drift of the machine shows up in both alike: `batch` segments x `gop` synthetic frames (the
 bench's content) per step through Av1GpuEngine.encode_gop + the OBU writer pool.  Prints one
-JSON line per timed run (frames/s, bytes, PSNR of the last step, CfL blocks of the last step) and
+JSON line per timed run (frames/s, bytes, PSNR of the last step, blocks of the last step that use
+the tool: CfL blocks, or blocks with a non-zero angle delta) and
 a summary with the medians.
 """
 from __future__ import annotations
@@ -27,6 +30,7 @@ sys.path.insert(0, ROOT)
 
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--name", choices=("cfl", "dir_intra"), default="cfl", help="the tool that is switched")
     ap.add_argument("--res", default="1920x1080")
     ap.add_argument("--qindex", type=int, default=100)
     ap.add_argument("--gop", type=int, default=64, help="frames per segment (2: key-frame heavy; 64: the bench's GOP)")
@@ -51,7 +55,7 @@ def main() -> None:
     w, h = map(int, a.res.split("x"))
     seed = 1 | ((1 << 31) if a.textured else 0)
     states = [a.tool] if a.tool else ["off", "on"]
-    engs = {s: Av1GpuEngine(w, h, batch=a.batch, qindex=a.qindex, intra_in_inter=a.intra_in_inter, cfl=s == "on")
+    engs = {s: Av1GpuEngine(w, h, batch=a.batch, qindex=a.qindex, intra_in_inter=a.intra_in_inter, **{a.name: s == "on"})
             for s in states}
     lib = stage._lib()
 
@@ -71,6 +75,12 @@ def main() -> None:
         g = eng.encode_gop(a.gop, load)
         return g, [b"".join(f.result()) for f in eng.submit_entropy(g)]
 
+    def tool_blocks(mode) -> int:
+        if a.name == "cfl":
+            return int(av1.mode_cfl(mode)[0].sum())
+        _, yd, _, uvd = av1.mode_angles(mode)
+        return int(((yd != 0) | (uvd != 0)).sum())
+
     def timed(state: str, first: int) -> dict:
         eng = engs[state]
         torch.cuda.synchronize(eng.dev)
@@ -81,7 +91,7 @@ def main() -> None:
         ps = eng.psnr(g)
         return {"tool": state, "frames_per_s": round(a.steps * a.batch * a.gop / dt, 1),
                 "last_step_bytes": sum(len(s) for s in segs), "last_step_psnr": {k: round(v, 4) for k, v in ps.items()},
-                "last_step_cfl_blocks": int(av1.mode_cfl(g.mode)[0].sum()),
+                "last_step_cfl_blocks" if a.name == "cfl" else "last_step_angled_blocks": tool_blocks(g.mode),
                 "last_step_intra_blocks": int(((np.asarray(g.mode) & 1) == 0).sum())}
 
     try:
@@ -105,7 +115,7 @@ def main() -> None:
         summary["on_over_off"] = round(med["on"] / med["off"], 4)
     print(json.dumps(summary), flush=True)
     if a.out:
-        cfg = {k: getattr(a, k) for k in ("res", "qindex", "gop", "batch", "textured", "intra_in_inter", "steps", "warmup")}
+        cfg = {k: getattr(a, k) for k in ("name", "res", "qindex", "gop", "batch", "textured", "intra_in_inter", "steps", "warmup")}
         with open(a.out, "w") as f:
             json.dump({"config": cfg, "runs": runs, "median_frames_per_s": med}, f, indent=1)
 

@@ -234,6 +234,30 @@ for nm, (dims, n, rows) in T.items():
         in_dav1d(nm, [r for r in rows if r and any(r)], n)
 
 
+def bits16(p: int) -> int:
+    """Rate of a symbol of probability p / 32768 in 1/16 bit: 16 * log2(32768 / p) rounded half
+    up, in exact integers: the n with 2^(2n - 1) <= (32768 / p)^32 < 2^(2n + 1)."""
+    assert 0 < p <= 32768
+    m = 480 - (p ** 32 - 1).bit_length()  # floor(32 * log2(32768 / p))
+    return (m + 1) >> 1
+
+
+def rate_rows(rows, n) -> list:
+    """bits16 of every symbol of n-symbol CDF rows (cumulative, n - 1 values each)."""
+    out = []
+    for r in rows:
+        c = [0] + list(r) + [32768]
+        out.append([bits16(c[k + 1] - c[k]) for k in range(n)])
+    return out
+
+
+# Rate tables of the opt-in directional intra search (tv/av1_enc.h "directional intra"): the
+# default CDFs' symbol costs, emitted next to the CDFs they come from.  y_mode: size group 2
+# (16x16 blocks) only.
+RATES = {"kf_y_mode": ((5, 5), lambda rows: rows), "y_mode": ((), lambda rows: rows[2:3]),
+         "uv_mode1": ((13,), lambda rows: rows), "angle_delta": ((8,), lambda rows: rows)}
+
+
 def emit() -> str:
     L = ["// av1_tables.h — GENERATED by tools/av1_tables_gen.py; do not edit.",
          "// Constant tables of the AV1 specification used by the encoder (8-bit), read out of the",
@@ -265,6 +289,18 @@ def emit() -> str:
             L.append("    " + ", ".join(body[i:i + 4]) + ",")
         L.append("};")
         L.append("")
+        if nm in RATES:
+            rdims, pick = RATES[nm]
+            rr = rate_rows(pick(rows), n)
+            assert max(max(r) for r in rr) < 256
+            rshape = "".join(f"[{d}]" for d in rdims)
+            L.append(f"// {nm}: symbol rates in 1/16 bit, round(16 * log2(32768 / p)) {list(rdims)}")
+            L.append(f"constexpr uint8_t {cname}Bits16{rshape}[{n}] = {{")
+            rbody = [", ".join(str(v) for v in r) for r in rr]
+            for i in range(0, len(rbody), 4):
+                L.append("    " + ", ".join(rbody[i:i + 4]) + ",")
+            L.append("};")
+            L.append("")
     L += ["}  // namespace tab", "}  // namespace av1", "}  // namespace tv", ""]
     return "\n".join(L)
 

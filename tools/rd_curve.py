@@ -27,6 +27,11 @@ def run_point(args):
     frames = [hevc.synth_frame(seed, t, w, h) for t in range(a["frames"])]
     if a.get("cut"):  # frames from `cut` on come from an unrelated seed and start: a cut inside the GOP
         frames[a["cut"]:] = [hevc.synth_frame(seed + 16, 40 + t, w, h) for t in range(a["cut"], a["frames"])]
+    if a.get("fan"):  # oriented gratings stepping through the directional angles, e.g. for --dir-intra
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        from av1_dir_cases import cut_clip, fan_clip
+
+        frames = cut_clip(w, h, a["frames"], a["cut"]) if a.get("cut") else fan_clip(w, h, a["frames"])
     if a.get("chroma_k"):  # chroma that follows luma (av1.correlated_chroma), e.g. for --cfl
         from thinvids_amd.models import av1 as _av1
 
@@ -58,7 +63,8 @@ def run_point(args):
             if fq is not None:  # a QP cascade in HEVC QP units, mapped to q-indices
                 qm = [av1.qindex_for_hevc_qp(x) for x in fq[s0:s0 + n]]
             r = av1.golden_encode(frames[s0:s0 + a["gop"]], w, h, q, qmap=qm,
-                                  intra_in_inter=a.get("intra_in_inter", False), cfl=a.get("cfl", False))
+                                  intra_in_inter=a.get("intra_in_inter", False), cfl=a.get("cfl", False),
+                                  dir_intra=a.get("dir_intra", False))
             stream += r.stream
             ys += [hevc.psnr(f[0], rec[:W * H].reshape(H, W)[:h, :w]) for f, rec in zip(frames[s0:], r.recon)]
             for f, rec in zip(frames[s0:], r.recon):  # chroma MSE for the 6:1:1 PSNR-YUV
@@ -127,6 +133,8 @@ def main():
     ap.add_argument("--sign-hiding", type=int, default=0, help="sign data hiding (tv/sdh.h)")
     ap.add_argument("--intra-in-inter", type=int, default=0, help="av1: intra blocks in inter frames (tv/av1_enc.h)")
     ap.add_argument("--cfl", type=int, default=0, help="av1: chroma from luma (tv/av1_enc.h)")
+    ap.add_argument("--dir-intra", type=int, default=0, help="av1: directional intra angles, CDF-based mode rates (tv/av1_enc.h)")
+    ap.add_argument("--fan", type=int, default=0, help="av1: replace the clip by the oriented-grating clip of tests/av1_dir_cases.py")
     ap.add_argument("--chroma-k", default="", help="KU,KV: replace the clip's chroma by one that follows its luma "
                     "(U = 128 + KU * (Y2x2 - 128) / 8 + noise; models/av1.py correlated_chroma)")
     ap.add_argument("--metric", choices=("y", "yuv"), default="y", help="BD-rate on PSNR-Y or (av1) on the 6:1:1 PSNR-YUV")
@@ -140,7 +148,7 @@ def main():
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
                ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
                sign_hiding=bool(a.sign_hiding), intra_in_inter=bool(a.intra_in_inter), cut=a.cut,
-               engine=a.engine, cfl=bool(a.cfl), chroma_k=[int(x) for x in a.chroma_k.split(",")] if a.chroma_k else [])
+               engine=a.engine, cfl=bool(a.cfl), dir_intra=bool(a.dir_intra), fan=bool(a.fan), chroma_k=[int(x) for x in a.chroma_k.split(",")] if a.chroma_k else [])
     qps = [int(q) for q in a.qps.split(",")]
     if a.engine == "gpu":
         pts = [run_point((q, cfg)) for q in qps]
