@@ -120,6 +120,7 @@ struct Cdfs {
   C17 new_mv[6], zero_mv[2], ref_mv[6], drl[3];
   C17 mv_joint, mv_sign[2], mv_class[2], class0_bit[2], class0_fr[2][2], mv_fr[2], mv_bits[2][10];
   C17 intra_tx[4][13], inter_tx[4];
+  C17 txfm_split[21], tx_size[3];  // tx_size: the 16x16 category (max depth 2) by context
   C17 txb_skip[5][13], eob_pt[7][2][2], eob_extra[5][2][9], base_eob[5][2][4], base[5][2][42], br[4][2][21];
   C17 dc_sign[2][3];
   C17 use_sgrproj;
@@ -161,6 +162,8 @@ template <class F> void visit_cdfs(Cdfs& c, F f) {
   each(c.mv_bits, 2, f);
   each(c.intra_tx, 5, f);
   each(c.inter_tx, 2, f);
+  each(c.txfm_split, 2, f);
+  each(c.tx_size, 3, f);
   each(c.txb_skip, 2, f);
   for (int s = 0; s < 7; ++s) each(c.eob_pt[s], s + 5, f);
   each(c.eob_extra, 2, f);
@@ -211,6 +214,8 @@ void init_cdfs(Cdfs& c, int qidx) {
   }
   for (int t = 0; t < 4; ++t) set_cdfs(c.intra_tx[t], kIntraTxSet2[t][0], 4, 5);
   set_cdfs(c.inter_tx, kInterTxSet3[0], 1, 2);
+  set_cdfs(c.txfm_split, kTxfmSplit[0], 1, 2);
+  set_cdfs(c.tx_size, kTxSizeCat123[0][0], 2, 3);
   set_cdf(c.use_sgrproj, kUseSgrproj, 2);
   const int q = coeff_qctx(qidx);
   for (int t = 0; t < 5; ++t) {
@@ -287,6 +292,10 @@ struct Tile {
   std::vector<uint8_t> ymode, coded;      // inter mode (NEARESTMV..NEWMV) or intra y mode
   std::vector<int8_t> cdef_seen;
   std::vector<uint8_t> aLvl[3], aDc[3], lLvl[3], lDc[3];
+  // transform-width contexts (above) / transform-height contexts (left) per 4x4 unit, in samples;
+  // 64 where nothing was coded yet (TX_MODE_SELECT frames: av1_enc.h "transform split")
+  std::vector<uint8_t> aTx, lTx;
+  bool tx_select = false;
   // level access: writer reads, reader writes (full layout [nblk][N*N])
   std::function<const int16_t*(int, int)> lev_in;
   const int16_t* eob_in[3] = {nullptr, nullptr, nullptr};  // writer: eob per packed TB (scan_packed)
@@ -302,6 +311,9 @@ struct Tile {
     ymode.assign(g.nblk(), 0);
     coded.assign(g.nblk(), 0);
     cdef_seen.assign(g.nsb(), -1);
+    tx_select = fp_.tx_select && !fp_.key;
+    aTx.assign(MiCols, 64);
+    lTx.assign(MiRows, 64);
     for (int p = 0; p < 3; ++p) {
       const int ss = p ? 1 : 0;
       aLvl[p].assign(MiCols >> ss, 0);
@@ -343,14 +355,29 @@ struct Tile {
   // scan-packed layout), the contexts read a zero-padded raster of the coded magnitudes
   // (stride N + 4: no bounds checks) that is cleared again at the eob positions only.
   uint8_t qpad_[20 * 20] = {};
-  void coeffs_w(int plane, int lg, int x4, int y4, const int16_t* lv, int eob, bool is_inter, int intra_dir) {
+  // txb_skip context of a luma TB smaller than its block (the general luma context): from the
+  // largest level context above and left of the TB
+  int luma_skip_ctx(int x4, int y4, int w4) const {
+    int top = 0, left = 0;
+    for (int i = 0; i < w4; ++i) {
+      if (x4 + i < (int)aLvl[0].size()) top = std::max<int>(top, aLvl[0][x4 + i]);
+      if (y4 + i < (int)lLvl[0].size()) left = std::max<int>(left, lLvl[0][y4 + i]);
+    }
+    if (!top && !left) return 1;
+    if (!top || !left) return 2 + (std::max(top, left) > 3);
+    if (std::max(top, left) <= 3) return 4;
+    return std::min(top, left) <= 3 ? 5 : 6;
+  }
+  // sub: a luma TB smaller than its block (a quadrant of a transform-split block)
+  void coeffs_w(int plane, int lg, int x4, int y4, const int16_t* lv, int eob, bool is_inter, int intra_dir,
+                bool sub = false) {
     const int N = 1 << lg, area = N * N, w4 = N >> 2, ptype = plane > 0, txc = lg - 2, S = N + 4;
     auto& AL = aLvl[plane];
     auto& AD = aDc[plane];
     auto& LL = lLvl[plane];
     auto& LD = lDc[plane];
     const int na = std::max(0, std::min(w4, (int)AL.size() - x4)), nl = std::max(0, std::min(w4, (int)LL.size() - y4));
-    int ctx = 0;
+    int ctx = sub ? luma_skip_ctx(x4, y4, w4) : 0;
     if (plane) {
       int above = 0, left = 0;
       for (int i = 0; i < na; ++i) above |= AL[x4 + i] | AD[x4 + i];
@@ -454,14 +481,15 @@ struct Tile {
   }
 
   // one transform block; L = raster levels (writer: input, reader: output)
-  void coeffs(int plane, int lg, int x4, int y4, int16_t* L, bool is_inter, int intra_dir, int eob_hint = -1) {
+  void coeffs(int plane, int lg, int x4, int y4, int16_t* L, bool is_inter, int intra_dir, int eob_hint = -1,
+              bool sub = false) {
     const int N = 1 << lg, area = N * N, w4 = N >> 2, ptype = plane > 0, txc = lg - 2;
     const int16_t* scan = lg == 4 ? scans().s16 : scans().s8;
     auto& AL = aLvl[plane];
     auto& AD = aDc[plane];
     auto& LL = lLvl[plane];
     auto& LD = lDc[plane];
-    int ctx = 0;
+    int ctx = sub ? luma_skip_ctx(x4, y4, w4) : 0;
     if (plane) {
       int above = 0, left = 0;
       for (int i = 0; i < w4; ++i) {
@@ -973,10 +1001,46 @@ struct Tile {
       io.sym(inter, cdf.is_inter[ictx], 2);
     }
     if (bsl > 2 && !(skip && inter)) throw std::runtime_error("av1: merged blocks are skip inter blocks only");
+    const int wsplit = IO::kW ? mode_tx(mode[b]) : 0, wqmask = IO::kW ? (int)((mode[b] >> 15) & 15) : 0;
+    if (wsplit && (skip || !inter || bsl > 2 || !tx_select))
+      throw std::runtime_error(
+          "av1 writer: transform split on a skip, intra or merged block (or a frame without the tool)");
     if (inter) inter_modes(b, mir, mic, availU, availL);
     else intra_modes(b, kf, availU, availL);
+    // transform size (read_block_tx_size; av1_enc.h "transform split")
+    int split = 0;
+    if (tx_select) {
+      auto set_tx = [&](int r4, int c4, int n4, int px) {
+        for (int i = 0; i < n4; ++i) aTx[c4 + i] = lTx[r4 + i] = (uint8_t)px;
+      };
+      if (inter && !skip) {  // read_var_tx_size: 16x16, then depth 1 (8x8); 4x4 is outside the subset
+        split = wsplit;
+        io.sym(split, cdf.txfm_split[12 + (aTx[mic] < 16) + (lTx[mir] < 16)], 2);
+        if (split) {
+          for (int k = 0; k < 4; ++k) {
+            const int r = mir + (k >> 1) * 2, c = mic + (k & 1) * 2;
+            int deeper = 0;
+            io.sym(deeper, cdf.txfm_split[15 + (aTx[c] < 8) + (lTx[r] < 8)], 2);
+            if (deeper) throw std::runtime_error("av1 oracle: 4x4 transforms are outside the encoder subset");
+            set_tx(r, c, 2, 8);
+          }
+        } else {
+          set_tx(mir, mic, 4, 16);
+        }
+      } else if (!inter) {  // read_tx_size: tx_depth 0 of the 16x16 category
+        int above = aTx[mic] >= 16, left = lTx[mir] >= 16;
+        if (availU && mode_inter(mode[b - g.bw])) above = (16 << mode_bsz(mode[b - g.bw])) >= 16;
+        if (availL && mode_inter(mode[b - 1])) left = (16 << mode_bsz(mode[b - 1])) >= 16;
+        int depth = 0;
+        io.sym(depth, cdf.tx_size[(availU ? above : 0) + (availL ? left : 0)], 3);
+        if (depth) throw std::runtime_error("av1 oracle: intra transform split is outside the encoder subset");
+        set_tx(mir, mic, 4, 16);
+      } else {  // skip inter blocks take their block size
+        set_tx(mir, mic, cur4, std::min(64, cur4 * 4));
+      }
+    }
     // residual
-    int nz = 0;
+    int nz = 0, qmask = 0;
     const int x4 = mic, y4 = mir;
     if (IO::kW && !skip) {
       for (int p = 0; p < 3; ++p) {
@@ -984,6 +1048,34 @@ struct Tile {
         const int16_t* lv = nullptr;
         int eob = 0;
         int16_t tmp[256];
+        if (p == 0 && split) {  // four 8x8 TBs in quadrant raster order
+          const int16_t* rec = scan_in[0] && scan_off[0][b] >= 0 ? scan_in[0] + scan_off[0][b] : nullptr;
+          const int16_t* src = scan_in[0] ? nullptr : lev_in(0, b);
+          for (int k = 0; k < 4; ++k) {
+            eob = 0;
+            lv = nullptr;
+            if (scan_in[0]) {  // the records of the nonzero quadrants back to back
+              if ((wqmask >> k & 1) && rec) {
+                eob = rec[0];
+                lv = rec + 1;
+                rec += 1 + eob;
+              }
+            } else if (src) {
+              for (int c = 0; c < 64; ++c) {
+                tmp[c] = src[k * 64 + scans().s8[c]];
+                if (tmp[c]) eob = c + 1;
+              }
+              lv = tmp;
+            }
+            if ((eob != 0) != ((wqmask >> k & 1) != 0))
+              throw std::runtime_error("av1 writer: quadrant mask of a transform-split block disagrees with its levels");
+            coeffs_w(0, 3, x4 + (k & 1) * 2, y4 + (k >> 1) * 2, lv, eob, true, ymode[b], true);
+            if (eob) qmask |= 1 << k;
+          }
+          if (!qmask) throw std::runtime_error("av1 writer: transform-split block with all-zero quadrants");
+          nz |= 1;
+          continue;
+        }
         if (scan_in[p]) {  // engine layout: [eob, levels in scan order] per nonzero TB
           const int32_t o = scan_off[p][b];
           if (o >= 0) {
@@ -1008,6 +1100,19 @@ struct Tile {
         const int lg = p ? 3 : 4;
         int16_t tmp[256];
         int16_t* L = tmp;
+        if (!IO::kW && p == 0 && split) {  // four 8x8 rasters in the block's 256 slots
+          for (int k = 0; k < 4; ++k) {
+            int16_t* Lq = lev_out[0] + ((size_t)b << 8) + k * 64;
+            coeffs(0, 3, x4 + (k & 1) * 2, y4 + (k >> 1) * 2, Lq, true, ymode[b], -1, true);
+            for (int i = 0; i < 64; ++i)
+              if (Lq[i]) {
+                qmask |= 1 << k;
+                break;
+              }
+          }
+          if (qmask) nz |= 1;
+          continue;
+        }
         if (IO::kW) {
           const int16_t* src = lev_in(p, b);
           if (src) std::memcpy(tmp, src, sizeof(int16_t) << (2 * lg));
@@ -1036,7 +1141,10 @@ struct Tile {
         if (!IO::kW) std::memset(lev_out[p] + ((size_t)b << (p ? 6 : 8)), 0, sizeof(int16_t) << (p ? 6 : 8));
       }
     }
-    if (!IO::kW) mode[b] = with_bsz((mode[b] & ~(7u << 10)) | ((uint32_t)nz << 10), bsl - 2);
+    if (!IO::kW) {
+      mode[b] = with_bsz((mode[b] & ~(7u << 10)) | ((uint32_t)nz << 10), bsl - 2);
+      if (split) mode[b] = with_tx_split(mode[b], qmask);
+    }
     const int n16 = 1 << (bsl - 2);  // 16x16 cells per side of this block
     for (int dy = 0; dy < n16; ++dy)
       for (int dx = 0; dx < n16; ++dx) {
@@ -1184,6 +1292,7 @@ struct Tile {
         std::fill(lLvl[p].begin(), lLvl[p].end(), 0);
         std::fill(lDc[p].begin(), lDc[p].end(), 0);
       }
+      std::fill(lTx.begin(), lTx.end(), 64);
       for (int sc = 0; sc < g.sbw; ++sc) {
         read_lr(sr, sc);
         partition(sr * 16, sc * 16, 4);
@@ -1350,7 +1459,8 @@ void write_frame_header(BitWriter& w, const SeqGeo& g, const FrameParams& fp, co
     w.put(0, 1);  // lr_unit_shift
     if (lr_type[1] || lr_type[2]) w.put(0, 1);  // lr_uv_shift
   }
-  w.put(0, 1);  // tx_mode_select (TX_MODE_LARGEST)
+  // tx_mode_select: TX_MODE_LARGEST, or TX_MODE_SELECT in the inter frames of a transform-split stream
+  w.put(fp.tx_select && !fp.key ? 1 : 0, 1);
   if (!fp.key) w.put(0, 1);  // reference_select
   w.put(1, 1);  // reduced_tx_set
   if (!fp.key)
@@ -1424,7 +1534,9 @@ FrameParams read_frame_header(BitReader& r, SeqGeo& g, bool& have_ref, int* lr_t
     expect(1, 0, "lr_unit_shift");
     if (lr_type[1] || lr_type[2]) expect(1, 0, "lr_uv_shift");
   }
-  expect(1, 0, "tx_mode_select");
+  fp.tx_select = (int)r.u(1);
+  if (fp.key && fp.tx_select)
+    throw std::runtime_error("av1 oracle: unsupported frame header tx_mode_select on a key frame");
   if (!fp.key) expect(1, 0, "reference_select");
   expect(1, 1, "reduced_tx_set");
   if (!fp.key)
@@ -1483,10 +1595,15 @@ std::vector<uint8_t> write_temporal_unit(const SeqGeo& g, const FrameDecisions& 
       int32_t o = 0;
       for (int b = 0; b < nb; ++b) {
         if (!(mode_nz(mode[b]) >> p & 1)) continue;
-        const int eob = base[p][o];
-        if (eob < 1 || eob > sz) throw std::runtime_error("scan-packed levels: bad eob");
         soff[p][b] = o;
-        o += 1 + eob;
+        // a transform-split block: the records of its nonzero quadrants back to back
+        const int nrec = p == 0 && mode_tx(mode[b]) ? __builtin_popcount(mode_txq(mode[b])) : 1;
+        const int lim = p == 0 && mode_tx(mode[b]) ? 64 : sz;
+        for (int k = 0; k < nrec; ++k) {
+          const int eob = base[p][o];
+          if (eob < 1 || eob > lim) throw std::runtime_error("scan-packed levels: bad eob");
+          o += 1 + eob;
+        }
       }
       t.scan_in[p] = base[p];
       t.scan_off[p] = soff[p].data();
@@ -1591,7 +1708,7 @@ void loop_filters(const SeqGeo& g, const FrameParams& fp, const uint32_t* mode, 
     for (int y = 0; y < h4; ++y)
       for (int x = 0; x < w4; ++x) {
         const uint32_t m = mode[(y / bs4) * g.bw + x / bs4];
-        info[(size_t)y * w4 + x] = lf_word(p > 0, lv, lh, mode_skip(m) && mode_inter(m), mode_bsz(m));
+        info[(size_t)y * w4 + x] = lf_word(p > 0, lv, lh, mode_skip(m) && mode_inter(m), mode_bsz(m), mode_tx(m) != 0);
       }
     const std::vector<uint8_t>& in = p == 0 ? rec.y : (p == 1 ? rec.u : rec.v);
     std::vector<uint8_t>& o = p == 0 ? db.y : (p == 1 ? db.u : db.v);
@@ -1679,7 +1796,13 @@ void reconstruct(const SeqGeo& g, const FrameDecisions& d, const Planes* ref, Pl
         int16_t res[256];
         predict(g, p, bx, by, m, mvw, rec, ref, pred);
         const bool nz = !mode_skip(m) && (mode_nz(m) >> p & 1) && off[p][b] >= 0;
-        if (nz) {
+        if (nz && p == 0 && mode_tx(m)) {  // four 8x8 rasters (av1_enc.h "transform split")
+          for (int k = 0; k < 4; ++k) {
+            int16_t r8[64];
+            residual_of(base[0] + (size_t)off[0][b] * 256 + k * 64, 3, d.fp.qindex, 0, r8);
+            for (int i = 0; i < 64; ++i) res[((k >> 1) * 8 + (i >> 3)) * 16 + (k & 1) * 8 + (i & 7)] = r8[i];
+          }
+        } else if (nz) {
           const int txt = p == 0 || mode_inter(m) ? 0 : uv_txtype(mode_uv(m));
           residual_of(base[p] + (size_t)off[p][b] * N * N, lg, d.fp.qindex, txt, res);
         } else {
@@ -1868,13 +1991,41 @@ int satd_block(const int* a, const int* b, int N) {
     }
   return s;
 }
+// Transform split of one inter block's luma (av1_enc.h "transform split"): the 16x16 coding
+// (levels lev16, reconstruction rec16) against the four 8x8 quadrants coded here.
+struct TxSplitTrial {
+  int16_t lev8[256];  // four 8x8 rasters, quadrant raster order
+  int rec8[256];      // block raster
+  int qmask, sse16, sse8, bits16, bits8, split;
+};
+void tx_split_trial(const int* src, const int* pred, int qidx, int rnd, const int16_t* lev16, const int* rec16,
+                    TxSplitTrial& t) {
+  t.qmask = t.sse16 = t.sse8 = 0;
+  t.bits16 = tx_tb_rate(lev16, 16);
+  t.bits8 = 0;
+  for (int k = 0; k < 4; ++k) {
+    int sq[64], pq[64], rq[64];
+    for (int i = 0; i < 64; ++i) {
+      const int o = ((k >> 1) * 8 + (i >> 3)) * 16 + (k & 1) * 8 + (i & 7);
+      sq[i] = src[o], pq[i] = pred[o];
+    }
+    if (code_tb(sq, pq, 3, qidx, 0, rnd, t.lev8 + k * 64, rq)) t.qmask |= 1 << k;
+    t.bits8 += tx_tb_rate(t.lev8 + k * 64, 8);
+    for (int i = 0; i < 64; ++i) t.rec8[((k >> 1) * 8 + (i >> 3)) * 16 + (k & 1) * 8 + (i & 7)] = rq[i];
+  }
+  for (int i = 0; i < 256; ++i) {
+    t.sse16 += (src[i] - rec16[i]) * (src[i] - rec16[i]);
+    t.sse8 += (src[i] - t.rec8[i]) * (src[i] - t.rec8[i]);
+  }
+  t.split = tx_split_wins(qidx, t.sse16, t.bits16, t.sse8, t.bits8, t.qmask);
+}
 }  // namespace
 
 GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qidx0, const int* qmap, int tools) {
   GoldenOut out;
   const int nb = g.nblk();
   // TV_AV1_DBG (conformance bring-up): 1 no deblocking, 2 no CDEF, 4 no loop restoration,
-  // 8 DC_PRED only, 16 no residual
+  // 8 DC_PRED only, 16 no residual, 128 (with kToolTxSplit) the pre-transform split rule
   const char* dbg_env = std::getenv("TV_AV1_DBG");
   const int dbg = dbg_env ? std::atoi(dbg_env) : 0;
   for (size_t f = 0; f < src.size(); ++f) {
@@ -1887,6 +2038,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
     const int lvl = (dbg & 1) ? 0 : lf_level_for_q(qidx);
     for (int i = 0; i < 4; ++i) fd.fp.lf[i] = lvl;
     fd.fp.cdef_damping = cdef_damping_for_q(qidx0);  // per stream (the engine's CDEF launches take one damping)
+    fd.fp.tx_select = (tools & kToolTxSplit) && f != 0;
     fd.mode.assign(nb, 0);
     fd.mv.assign(nb, 0);
     fd.ly.assign((size_t)nb * 256, 0);
@@ -1919,7 +2071,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
           for (int i = 0; i < N; ++i)
             for (int j = 0; j < N; ++j) s[p][i * N + j] = P[(size_t)(by * N + i) * w + bx * N + j];
         }
-        int ym = 0, uvm = 0, inter = 0, cfl_u = 0, cfl_v = 0;
+        int ym = 0, uvm = 0, inter = 0, cfl_u = 0, cfl_v = 0, split = 0, qmask = 0;
         uint32_t mvw = 0;
         // TV_AV1_DBG bit 32: the search also tries D113 / D135 / D157 (conformance tests of
         // the directional predictor; the shipped search leaves them out, av1_enc.h)
@@ -2056,6 +2208,28 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
             for (int i = 0; i < N * N; ++i) s[p][i] = pred[p][i];
           }
           if (code_tb(s[p], pred[p], lg, qidx, txt, inter ? frame_rnd : kRndIntra, lev, rc)) nz |= 1 << p;
+          if (p == 0 && inter && (tools & kToolTxSplit)) {  // transform split (av1_enc.h): the cheaper of the two
+            TxSplitTrial t;
+            tx_split_trial(s[0], pred[0], qidx, frame_rnd, lev, rc, t);
+            if (dbg & 128) {  // measurement: the pre-transform rule (quadrant SATD spread, as hevc rqt_split)
+              int sat4[4];
+              for (int k = 0; k < 4; ++k) {
+                int sq[64], pq[64];
+                for (int i = 0; i < 64; ++i) {
+                  const int o = ((k >> 1) * 8 + (i >> 3)) * 16 + (k & 1) * 8 + (i & 7);
+                  sq[i] = s[0][o], pq[i] = pred[0][o];
+                }
+                sat4[k] = satd_block(sq, pq, 8);
+              }
+              t.split = t.qmask != 0 && rqt_split(sat4, 64);
+            }
+            if (t.split) {
+              std::memcpy(lev, t.lev8, sizeof(t.lev8));
+              std::memcpy(rc, t.rec8, sizeof(t.rec8));
+              nz |= 1;
+              split = 1, qmask = t.qmask;
+            }
+          }
           std::vector<uint8_t>& P = p == 0 ? rec.y : (p == 1 ? rec.u : rec.v);
           for (int i = 0; i < N; ++i)
             for (int j = 0; j < N; ++j) P[(size_t)(by * N + i) * w + bx * N + j] = (uint8_t)rc[i * N + j];
@@ -2064,6 +2238,7 @@ GoldenOut golden_encode(const SeqGeo& g, const std::vector<Planes>& src, int qid
         if (uvm == UV_CFL_PRED) fd.mode[b] = with_cfl(fd.mode[b], cfl_u, cfl_v);
         else if (uvd) fd.mode[b] = with_angle_uv(fd.mode[b], uvd);
         if (yd) fd.mode[b] = with_angle_y(fd.mode[b], yd);
+        if (split) fd.mode[b] = with_tx_split(fd.mode[b], qmask);
         fd.mv[b] = inter ? mvw : 0;
     };
     if (fd.fp.key) {  // intra: left / above dependencies (raster order)
@@ -2290,7 +2465,7 @@ void split_planes(const uint8_t* yuv, const tv::av1::SeqGeo& g, tv::av1::Planes&
 // frame parameter vector of the C API: key, qindex, lf[4], sharp, damping, cdef_bits,
 // cdef_y[8], cdef_uv[8]
 void pack_fparams(const tv::av1::FrameParams& fp, int32_t* p) {
-  p[0] = fp.key;
+  p[0] = fp.key | (fp.tx_select << 1);  // bit 1: tx_mode_select of an inter frame
   p[1] = fp.qindex;
   for (int i = 0; i < 4; ++i) p[2 + i] = fp.lf[i];
   p[6] = fp.sharp;
@@ -2303,7 +2478,8 @@ void pack_fparams(const tv::av1::FrameParams& fp, int32_t* p) {
 }
 tv::av1::FrameParams unpack_fparams(const int32_t* p) {
   tv::av1::FrameParams fp;
-  fp.key = p[0];
+  fp.key = p[0] & 1;
+  fp.tx_select = (p[0] >> 1) & 1;
   fp.qindex = p[1];
   for (int i = 0; i < 4; ++i) fp.lf[i] = p[2 + i];
   fp.sharp = p[6];
@@ -2331,13 +2507,14 @@ int tv_av1c_qlookup(int q, int dc) { return dc ? dc_q(q) : ac_q(q); }
 
 // Encoder model constants (av1_enc.h) for the GPU engine's host side.  out [7 + kNumLrSets] =
 // kCdefMaskY, kCdefMaskUV, kMvMemoRecordBytes, kIbPasses, kToolIntraInInter, kToolCfl, then
-// the lr_set() values, then kToolDirIntra; returns kNumLrSets.
+// the lr_set() values, then kToolDirIntra, then kToolTxSplit; returns kNumLrSets.
 int tv_av1c_model_constants(int64_t* out) {
   const int64_t c[6] = {(int64_t)kCdefMaskY, (int64_t)kCdefMaskUV, kMvMemoRecordBytes, kIbPasses, kToolIntraInInter,
                         kToolCfl};
   for (int i = 0; i < 6; ++i) out[i] = c[i];
   for (int k = 0; k < kNumLrSets; ++k) out[6 + k] = lr_set(k);
   out[6 + kNumLrSets] = kToolDirIntra;
+  out[7 + kNumLrSets] = kToolTxSplit;
   return kNumLrSets;
 }
 // Per-q-index model values: out [3] = lf_level_for_q, lr_rate_cost, cdef_damping_for_q.
@@ -2351,7 +2528,8 @@ void tv_av1c_model_q(int q, int64_t* out) {
 // the temporal units go to `out` (one Bytes object) and their byte sizes to tu_sizes[n];
 // the post-filter reconstructions to recon (same layout); per-frame decisions to mode /
 // mv [n][nblk] and levels ly [n][nblk][256], lu / lv [n][nblk][64] (may be null).
-// tools: the coding-tools word (av1_enc.h kToolIntraInInter, kToolCfl); ib [n][nblk] (may be
+// tools: the coding-tools word (av1_enc.h kToolIntraInInter, kToolCfl, kToolDirIntra, kToolTxSplit);
+// ib [n][nblk] (may be
 // null): per frame and block, bit 0 = intra candidate, bit 1 = accepted.
 int tv_av1c_golden_encode(int dw, int dh, int n, const uint8_t* yuv, int qidx, const int* qmap, int tools, void* out,
                           int64_t* tu_sizes, uint8_t* recon, uint32_t* mode, uint32_t* mv, int16_t* ly, int16_t* lu,
@@ -2512,6 +2690,27 @@ int tv_av1c_dir_decide(int N, const uint8_t* src, const uint8_t* src_v, const ui
   });
 }
 
+// Transform-split decision of one inter block's luma (av1_enc.h "transform split"): src / pred
+// [256] (raster), q-index, inter rounding.  lev16 [256] / rec16 [256]: the 16x16 coding; lev8 [256]
+// (four 8x8 rasters, quadrant raster order) / rec8 [256] (block raster): the split coding.
+// out [7] = split (0 / 1), quadrant mask, sse16, bits16 of the 16x16 levels, sse8, bits16 of the
+// split levels (both without the flag terms), tx_lambda(q).
+int tv_av1c_tx_split_decide(const uint8_t* src, const uint8_t* pred, int qidx, int rnd, int16_t* lev16, uint8_t* rec16,
+                            int16_t* lev8, uint8_t* rec8, int64_t* out) {
+  return codec_guard([&] {
+    if (qidx < 1 || qidx > 255 || rnd < 0 || rnd > 64) throw std::runtime_error("av1: bad q-index / rounding");
+    int s[256], p[256], rc[256];
+    for (int i = 0; i < 256; ++i) s[i] = src[i], p[i] = pred[i];
+    code_tb(s, p, 4, qidx, 0, rnd, lev16, rc);
+    TxSplitTrial t;
+    tx_split_trial(s, p, qidx, rnd, lev16, rc, t);
+    std::memcpy(lev8, t.lev8, sizeof(t.lev8));
+    for (int i = 0; i < 256; ++i) rec16[i] = (uint8_t)rc[i], rec8[i] = (uint8_t)t.rec8[i];
+    const int64_t r[7] = {t.split, t.qmask, t.sse16, t.bits16, t.sse8, t.bits8, tx_lambda(qidx)};
+    std::memcpy(out, r, sizeof(r));
+  });
+}
+
 // Decode a stream (concatenated temporal units) -> up to max_frames coded-size frames.
 // geo[0..3] = display w, h, coded W, H; returns the frame count in *nframes.
 int tv_av1c_decode(const uint8_t* data, size_t n, int max_frames, uint8_t* frames, int* geo, int* nframes) {
@@ -2525,6 +2724,18 @@ int tv_av1c_decode(const uint8_t* data, size_t n, int max_frames, uint8_t* frame
     if (frames) {
       const size_t fsz = (size_t)d.geo.W * d.geo.H * 3 / 2;
       for (int i = 0; i < std::min(max_frames, (int)d.frames.size()); ++i) join_planes(d.frames[i], frames + i * fsz);
+    }
+  });
+}
+
+// The decoder oracle's mode and MV words of up to max_frames frames: mode / mv [frames][nblk].
+int tv_av1c_decode_modes(const uint8_t* data, size_t n, int max_frames, uint32_t* mode, uint32_t* mv) {
+  return codec_guard([&] {
+    Decoded d = decode_stream(data, n);
+    const size_t nb = (size_t)d.geo.nblk();
+    for (int i = 0; i < std::min(max_frames, (int)d.data.size()); ++i) {
+      std::memcpy(mode + i * nb, d.data[i].mode.data(), sizeof(uint32_t) * nb);
+      std::memcpy(mv + i * nb, d.data[i].mv.data(), sizeof(uint32_t) * nb);
     }
   });
 }

@@ -9,6 +9,9 @@
 //                  candidates x 16 4x4-SATD lanes per pass, 16-lane DPP reductions),
 //                  luma / chroma prediction, forward transform, quantisation,
 //                  dequantisation, the specification's inverse transform, reconstruction.
+//                  <TXS = true>: the opt-in transform-split instantiation of the recon stage
+//                  (kToolTxSplit): the luma residual also coded as four 8x8 transforms (one pair
+//                  of block-diagonal MFMA tile products), the cheaper coding kept.
 //   k_av1e_intra   one wave per 16x16 block of an anti-diagonal (key frames): the seven
 //                  candidate modes read no above-right samples, so the frame is a plain
 //                  (rows + cols - 1)-step wavefront; 4 luma modes x 16 lanes per pass, all
@@ -179,6 +182,145 @@ __device__ __forceinline__ int code_tb(int16_t* res, int16_t* a, int16_t* b, int
   return any ? 1 : 0;
 }
 
+// Transform split of one inter block's luma (tv/av1_enc.h "transform split"): the residual in
+// `res` is coded as one 16x16 transform and as four 8x8 transforms and the cheaper coding (J =
+// SSE + lambda * rate proxy, tx_split_wins) is kept: its levels go to lev_out (16x16 raster, or
+// four 8x8 rasters in quadrant order), its residual is left in `res`.  Returns 1 if any kept level
+// is nonzero; *txq = the nonzero quadrant mask when the split was kept, else -1.
+// The four 8x8 forward DCTs are one pair of exact 16x16 tile products with the block-diagonal
+// basis diag(D8, D8): diag(D8, D8) X transforms both 8-row halves, X' diag(D8, D8)^T finishes the
+// four quadrants (the 8x8 rounding shifts of txfm2d_ref): the eight MFMAs of the 16x16 transform.
+// The inverse is the specification's 8x8 process on 32 lanes (4 quadrants x 8 rows, then columns).
+// Scratch a / b / ti as code_tb; keep: LDS int16 [256], the residual's copy for the second coding.
+// sblk / predc: the block's source and prediction (LDS).
+__device__ __forceinline__ int code_luma_txs(int16_t* res, int16_t* a, int16_t* b, int32_t* ti, int16_t* keep,
+                                             const uint8_t* sblk, const int* predc, int qidx, int rnd,
+                                             int16_t* __restrict__ lev_out, int* txq) {
+  const int lane = threadIdx.x & 63, row0 = (lane >> 4) * 4, col = lane & 15;
+  const int qd = dc_q(qidx), qa = ac_q(qidx);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) keep[lane + 64 * j] = res[lane + 64 * j];
+  // ---- one 16x16 transform: levels and residual stay in registers
+  wave_txfm<4>(res, a, b, 0, 0, false);  // coefficients in b
+  int l16[4], r16[4], l8[4], nzl = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = lane + 64 * j;
+    l16[j] = quant(b[i], i ? qa : qd, rnd);
+    a[i] = (int16_t)dequant(l16[j], i ? qa : qd);
+    nzl |= l16[j] != 0;
+  }
+  const bool any16 = __any(nzl);
+  __syncthreads();
+  if (any16) {
+    if (lane < 16) {
+      int32_t in[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) in[j] = a[lane * 16 + j];
+      inv_row<4>(in, 0, ti + lane * 16);
+    }
+    __syncthreads();
+    if (lane < 16) {
+      int32_t t[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) t[i] = ti[i * 16 + lane];
+      inv_col<4>(t, 0);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) res[i * 16 + lane] = (int16_t)t[i];
+    }
+    __syncthreads();
+  }
+  int sse = 0, eob = 0, cnt = 0;  // cnt: nonzero levels << 20 | sum of their tx_level_bits16
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = lane + 64 * j;
+    r16[j] = any16 ? res[i] : 0;
+    const int d = (int)sblk[i] - clip_pixel(predc[i] + r16[j]);
+    sse += d * d;
+    if (l16[j]) {
+      eob = tv_max(eob, zigzag_index(16, i >> 4, i & 15) + 1);
+      cnt += (1 << 20) + tx_level_bits16(l16[j]);
+    }
+  }
+  const int sse16 = wave_sum(sse), c16s = wave_sum(cnt);
+  const int bits16 = tx_tb_bits16((int)~wave_min_u32(~(unsigned)eob), c16s >> 20, c16s & 0xFFFFF);
+  // ---- four 8x8 transforms: diag(D8, D8) on both sides of the kept residual
+  auto d8 = [&](int r, int k) -> int { return ((r ^ k) & 8) ? 0 : (int)c_dct8[(r & 7) * 8 + (k & 7)]; };
+  constexpr int f1 = 12 + (3 - 1) / 2 - 2, f2 = 12 + 3 / 2 - 1;
+  long long o[4];
+  __syncthreads();
+  exact_tile(d8, [&](int k, int c) { return (int)keep[k * 16 + c]; }, 0, 0, 16, o);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[(row0 + r) * 16 + col] = (int16_t)c16(rsr(o[r], f1));
+  __syncthreads();
+  exact_tile([&](int r, int k) { return (int)a[r * 16 + k]; }, [&](int k, int c) { return d8(c, k); }, 0, 0, 16, o);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) b[(row0 + r) * 16 + col] = (int16_t)c16(rsr(o[r], f2));
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = lane + 64 * j, q = ((i >> 4) | i) & 7 ? qa : qd;  // each quadrant has its DC
+    l8[j] = quant(b[i], q, rnd);
+    a[i] = (int16_t)dequant(l8[j], q);
+  }
+  __syncthreads();
+  {  // lanes 0..31: quadrant lane >> 3, its row / column lane & 7
+    const int q = (lane >> 3) & 3, k = lane & 7, r0 = (q >> 1) * 8, c0 = (q & 1) * 8;
+    if (lane < 32) {
+      int32_t in[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) in[j] = a[(r0 + k) * 16 + c0 + j];
+      inv_row<3>(in, 0, ti + (r0 + k) * 16 + c0);
+    }
+    __syncthreads();
+    if (lane < 32) {
+      int32_t t[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) t[i] = ti[(r0 + i) * 16 + c0 + k];
+      inv_col<3>(t, 0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) res[(r0 + i) * 16 + c0 + k] = (int16_t)t[i];
+    }
+    __syncthreads();
+  }
+  // a lane's elements: column half (lane >> 3) & 1, rows 0..7 for j < 2 and 8..15 for j >= 2
+  int eobh[2] = {0, 0}, cnth[2] = {0, 0};
+  sse = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = lane + 64 * j;
+    const int d = (int)sblk[i] - clip_pixel(predc[i] + res[i]);
+    sse += d * d;
+    if (l8[j]) {
+      eobh[j >> 1] = tv_max(eobh[j >> 1], zigzag_index(8, (i >> 4) & 7, i & 7) + 1);
+      cnth[j >> 1] += (1 << 20) + tx_level_bits16(l8[j]);
+    }
+  }
+  const int sse8 = wave_sum(sse), ch = (lane >> 3) & 1;
+  int bits8 = 0, qmask = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const bool mine = ch == (q & 1);
+    const int e = (int)~wave_min_u32(~(unsigned)(mine ? eobh[q >> 1] : 0)), c = wave_sum(mine ? cnth[q >> 1] : 0);
+    bits8 += tx_tb_bits16(e, c >> 20, c & 0xFFFFF);
+    qmask |= (e != 0) << q;
+  }
+  const bool split = tx_split_wins(qidx, sse16, bits16, sse8, bits8, qmask);  // wave-uniform
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = lane + 64 * j, r = i >> 4, c = i & 15;
+    if (split) {
+      lev_out[((r >> 3) * 2 + (c >> 3)) * 64 + (r & 7) * 8 + (c & 7)] = (int16_t)l8[j];
+    } else {
+      lev_out[i] = (int16_t)l16[j];
+      res[i] = (int16_t)r16[j];
+    }
+  }
+  __syncthreads();
+  *txq = split ? qmask : -1;
+  return split || any16 ? 1 : 0;
+}
+
 struct Planes3 {
   const uint8_t *y, *u, *v;
 };
@@ -193,7 +335,9 @@ struct Planes3W {
 // scratch, against the compiler's 84 / 5 waves); stage 1 is LDS-limited, left alone.
 // IC (stage 1 only): also write the block's inter cost (luma SATD of the source against the
 // prediction, tv/av1_enc.h "intra blocks in inter frames") to icost [B][nb].
-template <int STAGE, bool IC = false>
+// TXS (stage 1 only; kToolTxSplit, tv/av1_enc.h "transform split"): the luma residual is coded as
+// one 16x16 and as four 8x8 transforms and the cheaper is kept (code_luma_txs).
+template <int STAGE, bool IC = false, bool TXS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STAGE == 0 ? 6 : 1))) k_av1e_inter(Planes3 src, Planes3 ref, Planes3W rec, uint32_t* __restrict__ mode,
                                                    const uint32_t* __restrict__ mvin, uint32_t* __restrict__ mvout,
                                                    int16_t* __restrict__ ly, int16_t* __restrict__ lu,
@@ -429,7 +573,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STAGE =
     if (lane == 0) icost[bo] = sat;
   }
   const int rnd = inter_rounding((long long)satd_acc[b], W, H);
-  int nz = code_tb<4>(res, ta, tb, ti, 0, 0, qidx, rnd, ly + bo * 256);
+  int nz, txq = -1;
+  if constexpr (TXS) {
+    __shared__ int16_t rkeep[256];
+    nz = code_luma_txs(res, ta, tb, ti, rkeep, sblk, predc, qidx, rnd, ly + bo * 256, &txq);
+  } else {
+    nz = code_tb<4>(res, ta, tb, ti, 0, 0, qidx, rnd, ly + bo * 256);
+  }
   for (int i = lane; i < 256; i += 64)
     rec.y[b * ysz + (long)(y0 + (i >> 4)) * W + x0 + (i & 15)] = (uint8_t)clip_pixel(predc[i] + res[i]);
   __syncthreads();
@@ -454,7 +604,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(STAGE =
     __syncthreads();
   }
   if (lane == 0) {
-    mode[bo] = pack_mode(1, 0, 0, nz == 0, nz);
+    const uint32_t m = pack_mode(1, 0, 0, nz == 0, nz);
+    mode[bo] = TXS && txq >= 0 ? with_tx_split(m, txq) : m;
     mvout[bo] = pack_mv(mr, mc);
   }
 }
@@ -1053,7 +1204,7 @@ __global__ void k_av1e_lfinfo(const uint32_t* __restrict__ mode, int W, int H, c
   const uint32_t m = mode[(long)b * nb + (y >> 2) * bw + (x >> 2)];
   const bool si = mode_skip(m) && mode_inter(m);
   const int bz = mode_bsz(m);
-  iy[(long)b * w4 * h4 + u] = lf_word(false, lv0, lv1, si, bz);
+  iy[(long)b * w4 * h4 + u] = lf_word(false, lv0, lv1, si, bz, mode_tx(m) != 0);
   if (!(x & 1) && !(y & 1)) {
     const long cu = (long)b * (w4 / 2) * (h4 / 2) + (y >> 1) * (w4 / 2) + (x >> 1);
     iu[cu] = lf_word(true, lv2, lv2, si, bz);
@@ -1270,13 +1421,24 @@ __device__ __forceinline__ long tb_index(long tb, int nb, int nseg, int Bmax) {
 __global__ void __launch_bounds__(256) k_av1e_tb_len(const int16_t* __restrict__ lev,
                                                      const uint32_t* __restrict__ mode, long ntb, int nb, int nseg,
                                                      int Bmax, int p, int* __restrict__ len) {
-  __shared__ int16_t sc[256];
+  __shared__ int16_t sc[256], sc8[64];
   const int N2 = p ? 64 : 256, lane = threadIdx.x & 63;
   if (threadIdx.x == 0) zigzag_scan(p ? 8 : 16, sc);
+  if (threadIdx.x == 64) zigzag_scan(8, sc8);
   __syncthreads();
   for (long tb = (long)blockIdx.x * 4 + (threadIdx.x >> 6); tb < ntb; tb += (long)gridDim.x * 4) {
     const long mi = tb_index(tb, nb, nseg, Bmax);
     const bool nz = (mode[mi] >> (10 + p)) & 1;  // wave-uniform
+    if (p == 0 && nz && mode_tx(mode[mi])) {  // transform split: a record per nonzero 8x8 quadrant
+      int L = 0;
+      for (int q = 0; q < 4; ++q) {
+        if (!(mode_txq(mode[mi]) >> q & 1)) continue;
+        const unsigned l8 = lev[mi * 256 + q * 64 + sc8[lane]] ? lane + 1 : 0;
+        L += 1 + (int)~wave_min_u32(~l8);
+      }
+      if (lane == 0) len[tb] = L;
+      continue;
+    }
     int last = 0;                                  // scan index + 1 of the lane's last nonzero
     if (nz)
       for (int k = lane; k < N2; k += 64)
@@ -1285,17 +1447,31 @@ __global__ void __launch_bounds__(256) k_av1e_tb_len(const int16_t* __restrict__
     if (lane == 0) len[tb] = nz ? 1 + (int)eob : 0;
   }
 }
-__global__ void __launch_bounds__(256) k_av1e_tb_pack(const int16_t* __restrict__ lev, const int* __restrict__ len,
+__global__ void __launch_bounds__(256) k_av1e_tb_pack(const int16_t* __restrict__ lev,
+                                                      const uint32_t* __restrict__ mode, const int* __restrict__ len,
                                                       const long long* __restrict__ end, long ntb, int nb, int nseg,
                                                       int Bmax, int p, int16_t* __restrict__ out) {
-  __shared__ int16_t sc[256];
+  __shared__ int16_t sc[256], sc8[64];
   const int N2 = p ? 64 : 256, lane = threadIdx.x & 63;
   if (threadIdx.x == 0) zigzag_scan(p ? 8 : 16, sc);
+  if (threadIdx.x == 64) zigzag_scan(8, sc8);
   __syncthreads();
   for (long tb = (long)blockIdx.x * 4 + (threadIdx.x >> 6); tb < ntb; tb += (long)gridDim.x * 4) {
     const int L = len[tb];
     if (!L) continue;
     const long mi = tb_index(tb, nb, nseg, Bmax), o = end[tb] - L;
+    if (p == 0 && mode_tx(mode[mi])) {  // transform split: [eob, levels] of each nonzero quadrant
+      long oq = o;
+      for (int q = 0; q < 4; ++q) {
+        if (!(mode_txq(mode[mi]) >> q & 1)) continue;
+        const int16_t l = lev[mi * 256 + q * 64 + sc8[lane]];
+        const int eob = (int)~wave_min_u32(~(unsigned)(l ? lane + 1 : 0));
+        if (lane == 0) out[oq] = (int16_t)eob;
+        if (lane < eob) out[oq + 1 + lane] = l;
+        oq += 1 + eob;
+      }
+      continue;
+    }
     if (lane == 0) out[o] = (int16_t)(L - 1);
     for (int k = lane; k < L - 1; k += 64) out[o + 1 + k] = lev[mi * N2 + sc[k]];
   }
@@ -1315,10 +1491,11 @@ const char* tv_av1e_last_error() { return g_err.c_str(); }
 // goes through `tmp` ([B][nb] words): search -> tmp, kMvRefineRounds refinement rounds
 // ping-ponging between tmp and mv (ending in mv), then the recon at mv.  icost (may be null):
 // [B][nb], every block's inter cost (luma SATD at its final MV), the input of tv_av1e_iblocks.
-int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
+// tools: the coding-tools word (kToolTxSplit: the recon stage also tries the 8x8 transform split).
+int tv_av1e_inter_tools(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
                   const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv, uint32_t* tmp,
                   unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu, int16_t* lv, int* icost,
-                  int W, int H, int B, const int* qarr, void* stream) {
+                  int W, int H, int B, const int* qarr, int tools, void* stream) {
   if (bad(W, H, B, 1, "av1e_inter") || ensure_tables()) return -1;
   static_assert(kMvRefineRounds % 2 == 1, "an odd round count ends the field in `mv`");
   const int nb = (W >> 4) * (H >> 4), nsb = ((W + 63) >> 6) * ((H + 63) >> 6);
@@ -1342,13 +1519,20 @@ int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const
   }
   if (hipMemsetAsync(satd_acc, 0, (size_t)B * sizeof(unsigned long long), st) != hipSuccess) return status("av1e_inter");
   k_av1e_mv_unify<<<dim3(nsb, B), 256, 0, st>>>(sy, ry, mv, W, H, qarr, satd_acc);
-  if (icost)
-    k_av1e_inter<1, true><<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov},
-                                                      mode, mv, mv, ly, lu, lv, W, H, qarr, satd_acc, icost);
-  else
-    k_av1e_inter<1><<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov}, mode,
-                                                mv, mv, ly, lu, lv, W, H, qarr, satd_acc, nullptr);
+  const bool txs = tools & kToolTxSplit;
+  const auto recon = icost ? (txs ? k_av1e_inter<1, true, true> : k_av1e_inter<1, true, false>)
+                           : (txs ? k_av1e_inter<1, false, true> : k_av1e_inter<1, false, false>);
+  recon<<<dim3(nb, B), 64, 0, st>>>(Planes3{sy, su, sv}, Planes3{ry, ru, rv}, Planes3W{oy, ou, ov}, mode, mv, mv, ly, lu,
+                                    lv, W, H, qarr, satd_acc, icost);
   return status("av1e_inter");
+}
+// the same with no tool on
+int tv_av1e_inter(const uint8_t* sy, const uint8_t* su, const uint8_t* sv, const uint8_t* ry, const uint8_t* ru,
+                  const uint8_t* rv, uint8_t* oy, uint8_t* ou, uint8_t* ov, uint32_t* mode, uint32_t* mv, uint32_t* tmp,
+                  unsigned long long* satd_acc, uint8_t* memo, int16_t* ly, int16_t* lu, int16_t* lv, int* icost,
+                  int W, int H, int B, const int* qarr, void* stream) {
+  return tv_av1e_inter_tools(sy, su, sv, ry, ru, rv, oy, ou, ov, mode, mv, tmp, satd_acc, memo, ly, lu, lv, icost, W, H, B,
+                             qarr, 0, stream);
 }
 
 // Intra blocks of an inter frame (tv/av1_enc.h), between tv_av1e_inter and tv_av1e_merge:
@@ -1426,15 +1610,15 @@ int tv_av1e_tb_len(const int16_t* lev, const uint32_t* mode, long ntb, int nb, i
   return status("av1e_tb_len");
 }
 // end: inclusive prefix sum of len (int64); out sized end[ntb - 1]
-int tv_av1e_tb_pack(const int16_t* lev, const int* len, const long long* end, long ntb, int nb, int nseg, int Bmax,
-                    int p, int16_t* out, void* stream) {
+int tv_av1e_tb_pack(const int16_t* lev, const uint32_t* mode, const int* len, const long long* end, long ntb, int nb,
+                    int nseg, int Bmax, int p, int16_t* out, void* stream) {
   if (ntb < 0 || nb <= 0 || nseg <= 0 || nseg > Bmax || p < 0 || p > 2 || ntb % ((long)nb * nseg)) {
     g_err = "av1e_tb_pack: bad geometry";
     return -1;
   }
   if (!ntb) return 0;
   const long g = std::min((ntb + 3) / 4, 1L << 18);
-  k_av1e_tb_pack<<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(lev, len, end, ntb, nb, nseg, Bmax, p, out);
+  k_av1e_tb_pack<<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(lev, mode, len, end, ntb, nb, nseg, Bmax, p, out);
   return status("av1e_tb_pack");
 }
 

@@ -36,6 +36,7 @@ struct FrameParams {
   int cdef_bits = 3;
   uint8_t cdef_y[8] = {0};   // preset index pri * 4 + sec_idx (sec_idx 3 -> strength 4)
   uint8_t cdef_uv[8] = {0};
+  int tx_select = 0;         // inter frames: tx_mode_select (av1_enc.h "transform split"); 0 on key frames
 };
 
 // Decisions of one frame.  Levels are raster order inside each transform block.  A null

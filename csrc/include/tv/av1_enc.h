@@ -7,6 +7,8 @@
 //   * 64x64 superblocks, coded size padded to a multiple of 16 (render_size = display size);
 //     every superblock splits to 16x16 coding blocks (PARTITION_SPLIT / split_or_* at edges);
 //   * TX_MODE_LARGEST: one 16x16 luma and two 8x8 chroma transforms per block, reduced_tx_set;
+//     opt-in (kToolTxSplit, off by default): inter frames signal TX_MODE_SELECT and a non-skip
+//     inter block may code its luma as four 8x8 transforms ("transform split" below);
 //   * key frames: intra modes DC / V / H / SMOOTH / SMOOTH_V / SMOOTH_H / PAETH searched (D113 /
 //     D135 / D157 predicted and decodable too); all read no above-right / below-left samples,
 //     so the I-frame wavefront is a plain diagonal; angle delta 0; intra edge filter / filter
@@ -781,11 +783,93 @@ TV_HD int dir_uv_bits16(int ym, int uvm, int delta) { return tab::kUvMode1Bits16
 // y mode of a neighbour's mode word for the key-frame context
 TV_HD int dir_ctx_mode(uint32_t m) { return mode_inter(m) ? DC_PRED : mode_y(m); }
 
-// deblocking info word for a 4x4 unit (av1_defs.h layout): tx = block = 16 << bsz luma,
-// 8 << bsz chroma
-TV_HD uint32_t lf_word(bool chroma, int lvl_v, int lvl_h, bool skip_inter, int bsz = 0) {
-  const uint32_t l = (chroma ? 1u : 2u) + (uint32_t)bsz;
-  return l | (l << 3) | (l << 6) | (l << 9) | ((uint32_t)(lvl_v & 63) << 12) | ((uint32_t)(lvl_h & 63) << 18) |
+// ------------------------------------------------------------- transform split ----------
+// Opt-in tool (kToolTxSplit, off by default): a non-skip 16x16 inter block may code its luma as
+// four 8x8 DCT_DCT transforms instead of one 16x16 (chroma keeps its two 8x8 transforms).  With
+// the tool on, inter frames signal TX_MODE_SELECT; key frames keep TX_MODE_LARGEST, so the key
+// frame of a tool-on stream is the tool-off key frame.  With the tool off every stream, mode
+// word and kernel instruction is what it was.
+//   candidates  after prediction the luma residual is coded both ways with the frame's inter
+//               rounding: one 16x16 transform, and the four 8x8 quadrants (raster order, each
+//               with its own DC step).
+//   cost        J = (SSE(source, reconstruction) << 8) + tx_lambda(q) * bits16: bits16 (1/16
+//               bit) is a closed-form proxy over the quantised levels (tx_tb_bits16 per
+//               transform block: an all-zero flag, or a coded-block term, an eob-position term
+//               per bit of the eob, a term per zero before the eob and, per nonzero level, a
+//               base plus a term per floor(log2 |l|)), plus the txfm_split symbols from the
+//               default CDFs (tv/av1_tables.h kTxfmSplitBits16): split = the 16x16 flag (context
+//               12: neighbours with transforms of 16 or more) + four 8x8 "no further split" flags
+//               (context 15); kept = the 16x16 flag alone.  tx_lambda(q) = 9 * ac_q^2 / 64, the
+//               SSE-per-bit slope of lr_rate_cost in these units.
+//   decision    split when J(split) < J(16x16) and at least one quadrant has a nonzero level;
+//               ties keep 16x16.  A pure function of the block's source, prediction and q: inter
+//               frames stay embarrassingly parallel.  A block whose chosen luma and chroma are
+//               all zero is a skip block and never carries the split bit.
+//   mode word   bit 30 = split, bits 15-18 = nonzero mask of the quadrants (raster order; those
+//               bits hold intra-only fields otherwise and are zero for inter blocks).  Bit 10
+//               (Y) of a split block is set, and its 256 luma level slots hold four 8x8 rasters.
+//   syntax      read_block_tx_size: txfm_split at 16x16 and, if 1, one txfm_split = 0 per 8x8
+//               (depth 1; 4x4 is never coded); intra blocks of such frames code tx_depth = 0.
+//               Each 8x8 luma TB codes txb_skip with the general luma context.
+//   deblocking  luma transform size 8 for the 4x4 units of a split block (lf_word).
+// Constants: profiles/av1_tx_split/README.md.
+constexpr int kToolTxSplit = 8;  // bit of the encoders' tools word
+constexpr int kTxTbZeroBits16 = 8, kTxTbCodedBits16 = 24, kTxEobBits16 = 24, kTxZeroCoefBits16 = 10;
+constexpr int kTxLevelBits16 = 40, kTxLevelLogBits16 = 32;
+constexpr int kTxSplitCtx16 = 12, kTxSplitCtx8 = 15;  // txfm_split contexts the rate term reads
+TV_HD int mode_tx(uint32_t m) { return (int)((m >> 30) & 1); }
+TV_HD int mode_txq(uint32_t m) { return mode_tx(m) ? (int)((m >> 15) & 15) : 0; }
+TV_HD uint32_t with_tx_split(uint32_t m, int qmask) {
+  return (m & ~((15u << 15) | (1u << 30))) | (1u << 30) | ((uint32_t)(qmask & 15) << 15);
+}
+// scan index (zigzag_scan order) of raster position (r, c) of an N x N block
+TV_HD int zigzag_index(int N, int r, int c) {
+  const int s = r + c;
+  const int before = s < N ? s * (s + 1) / 2 : N * N - (2 * N - 1 - s) * (2 * N - s) / 2;
+  const int lo = s - N + 1 > 0 ? s - N + 1 : 0, hi = s < N - 1 ? s : N - 1;
+  return before + ((s & 1) ? r - lo : hi - r);
+}
+TV_HD int tx_level_bits16(int l) {
+  const int a = l < 0 ? -l : l;
+  return a ? kTxLevelBits16 + kTxLevelLogBits16 * (tv_bitlen((unsigned)a) - 1) : 0;
+}
+// rate of one transform block from its eob (scan index of the last nonzero level + 1), its
+// count of nonzero levels and the sum of their tx_level_bits16
+TV_HD int tx_tb_bits16(int eob, int nnz, int level_bits) {
+  if (!eob) return kTxTbZeroBits16;
+  return kTxTbCodedBits16 + kTxEobBits16 * tv_bitlen((unsigned)eob) + kTxZeroCoefBits16 * (eob - nnz) + level_bits;
+}
+TV_HD int tx_split_flag_bits16(bool split) {
+  return split ? tab::kTxfmSplitBits16[kTxSplitCtx16][1] + 4 * tab::kTxfmSplitBits16[kTxSplitCtx8][0]
+               : tab::kTxfmSplitBits16[kTxSplitCtx16][0];
+}
+TV_HD int tx_lambda(int q) { return (ac_q(q) * ac_q(q) * 9) >> 6; }
+TV_HD long long tx_cost(int sse, int bits16, int q) { return ((long long)sse << 8) + (long long)tx_lambda(q) * bits16; }
+// sse / bits16 of the two codings (bits16 without the flag terms); qmask8 = nonzero quadrants
+TV_HD bool tx_split_wins(int q, int sse16, int bits16_16, int sse8, int bits16_8, int qmask8) {
+  return qmask8 != 0 && tx_cost(sse8, bits16_8 + tx_split_flag_bits16(true), q) <
+                            tx_cost(sse16, bits16_16 + tx_split_flag_bits16(false), q);
+}
+// rate of the N x N raster levels of one transform block
+TV_HD int tx_tb_rate(const int16_t* lev, int N) {
+  int eob = 0, nnz = 0, lb = 0;
+  for (int r = 0; r < N; ++r)
+    for (int c = 0; c < N; ++c) {
+      const int l = lev[r * N + c];
+      if (!l) continue;
+      const int k = zigzag_index(N, r, c) + 1;
+      eob = k > eob ? k : eob;
+      ++nnz;
+      lb += tx_level_bits16(l);
+    }
+  return tx_tb_bits16(eob, nnz, lb);
+}
+
+// deblocking info word for a 4x4 unit (av1_defs.h layout): block = 16 << bsz luma, 8 << bsz
+// chroma; tx = block, or 8 for the luma of a transform-split block
+TV_HD uint32_t lf_word(bool chroma, int lvl_v, int lvl_h, bool skip_inter, int bsz = 0, bool split = false) {
+  const uint32_t l = (chroma ? 1u : 2u) + (uint32_t)bsz, t = split && !chroma ? 1u : l;
+  return t | (t << 3) | (l << 6) | (l << 9) | ((uint32_t)(lvl_v & 63) << 12) | ((uint32_t)(lvl_h & 63) << 18) |
          ((uint32_t)skip_inter << 24);
 }
 

@@ -95,7 +95,9 @@ CORE = {
     "tv_av1c_dir_tables": (None, [i32p] * 5),
     "tv_av1c_dir_cands": (None, [i32p]),
     "tv_av1c_dir_decide": (i, [i, u8p, u8p, u8p, u8p, i, i, i, i, i, i, i, i32p, i32p]),
+    "tv_av1c_tx_split_decide": (i, [u8p, u8p, i, i, i16p, u8p, i16p, u8p, i64p]),
     "tv_av1c_decode": (i, [u8p, sz, i, u8p, i32p, i32p]),
+    "tv_av1c_decode_modes": (i, [u8p, sz, i, u32p, u32p]),
     "tv_av1c_probe": (i, [u8p, sz, i32p, i32p]),
     "tv_av1c_state_new": (vp, []),
     "tv_av1c_state_free": (None, [vp]),
@@ -182,12 +184,13 @@ GPU = {
     # k_av1_enc.hip: the AV1 engine (device pointers, stream last)
     "tv_av1e_last_error": (cstr, []),
     "tv_av1e_inter": (i, [vp] * 18 + [i, i, i, vp, vp]),
+    "tv_av1e_inter_tools": (i, [vp] * 18 + [i, i, i, vp, i, vp]),
     "tv_av1e_iblocks": (i, [vp] * 16 + [i, i, i, vp, i, vp]),
     "tv_av1e_intra": (i, [vp] * 11 + [i, i, i, vp, i, vp]),
     "tv_av1e_cdef_skip": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_merge": (i, [vp, vp, i, i, i, vp]),
     "tv_av1e_tb_len": (i, [vp, vp, l, i, i, i, i, vp, vp]),
-    "tv_av1e_tb_pack": (i, [vp, vp, vp, l, i, i, i, i, vp, vp]),
+    "tv_av1e_tb_pack": (i, [vp, vp, vp, vp, l, i, i, i, i, vp, vp]),
     "tv_av1e_lfinfo": (i, [vp, i, i, i, vp, vp, vp, vp, vp]),
     "tv_av1e_unit_sse": (i, [vp, vp, i, i, i, i, i, vp, vp]),
     "tv_av1e_cdef_choose": (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]),

@@ -11,6 +11,8 @@ current HIP stream:
                  coder also tries chroma from luma]
                 [dir_intra: their <DIR = true> instantiations, whose mode searches run over 34
                  (mode, angle delta) candidates with rates from the default CDFs]
+                [tx_split: the <TXS = true> instantiation of k_av1e_inter's recon stage, which codes
+                 the luma residual as one 16x16 and as four 8x8 transforms and keeps the cheaper]
     both        k_av1e_lfinfo -> k_deblock (Y, U, V) -> k_cdef_dir -> k_av1e_cdef_skip ->
                 k_cdef_search (Y, U, V) -> k_av1e_cdef_choose -> k_cdef_apply -> next reference
 
@@ -52,6 +54,7 @@ def _model():
     for i in range(256):
         lib.tv_av1c_model_q(i, q[i].ctypes.data_as(C.POINTER(C.c_int64)))
     assert c[6 + nsets] == av1m.TOOL_DIR_INTRA  # appended after the lr sets (kToolDirIntra)
+    assert c[7 + nsets] == av1m.TOOL_TX_SPLIT  # then kToolTxSplit
     return list(c[:6]) + [tuple(c[6:6 + nsets])], q
 
 
@@ -142,21 +145,25 @@ class Av1GpuEngine:
 
     def __init__(self, width: int, height: int, batch: int, qindex: int = 100, device: int = 0,
                  threads: int | None = None, cascade: bool = True, intra_in_inter: bool = False,
-                 cfl: bool = False, dir_intra: bool = False):
+                 cfl: bool = False, dir_intra: bool = False, tx_split: bool = False):
         """`intra_in_inter` (off by default): 16x16 blocks of inter frames may be coded as intra
         blocks (av1_enc.h "intra blocks in inter frames"; k_av1e_ib_*), as the golden encoder
         does with the same flag.  `cfl` (off by default): intra blocks may predict chroma from
         their reconstructed luma (av1_enc.h "chroma from luma"; the CFL instantiations of
         k_av1e_intra / k_av1e_ib_recon).  `dir_intra` (off by default): the intra mode searches run
         over every directional angle strictly between 90 and 180 degrees with CDF-based rates
-        (av1_enc.h "directional intra"; the DIR instantiations of the same kernels)."""
+        (av1_enc.h "directional intra"; the DIR instantiations of the same kernels).  `tx_split`
+        (off by default): non-skip inter blocks may code their luma as four 8x8 transforms
+        (av1_enc.h "transform split"; the TXS instantiation of k_av1e_inter)."""
         import torch
 
         self.intra_in_inter = bool(intra_in_inter)
         self.cfl = bool(cfl)
         self.dir_intra = bool(dir_intra)
+        self.tx_split = bool(tx_split)
         # the kernels' tools word (intra_in_inter is a launch of its own)
-        self.tools = (TOOL_CFL if self.cfl else 0) | (av1m.TOOL_DIR_INTRA if self.dir_intra else 0)
+        self.tools = ((TOOL_CFL if self.cfl else 0) | (av1m.TOOL_DIR_INTRA if self.dir_intra else 0) |
+                      (av1m.TOOL_TX_SPLIT if self.tx_split else 0))
         self.cascade = bool(cascade)  # constant q: the low-delay q cascade (av1.cascade_qmap)
         self.torch = torch
         self.w, self.h, self.B, self.q = width, height, batch, int(qindex)
@@ -233,9 +240,9 @@ class Av1GpuEngine:
                                   self.tools, st))
         else:
             icost = ws["ibcost"] if self.intra_in_inter else None
-            _ok(lib.tv_av1e_inter(*map(_p, src), *map(_p, fin), *map(_p, rec), _p(mode), _p(mv), _p(ws["mvtmp"]),
-                                  _p(ws["satd"]), _p(self._ws["memo"]), *map(_p, lev),
-                                  None if icost is None else _p(icost), W, H, B, _p(qarr), st))
+            _ok(lib.tv_av1e_inter_tools(*map(_p, src), *map(_p, fin), *map(_p, rec), _p(mode), _p(mv),
+                                        _p(ws["mvtmp"]), _p(ws["satd"]), _p(self._ws["memo"]), *map(_p, lev),
+                                        None if icost is None else _p(icost), W, H, B, _p(qarr), self.tools, st))
             if self.intra_in_inter:
                 _ok(lib.tv_av1e_iblocks(*map(_p, src), *map(_p, rec), _p(mode), _p(mv), *map(_p, lev), _p(icost),
                                         _p(ws["ibcand"]), _p(G["ib"][t, :B]), _p(ws["ibcnt"]), _p(ws["iblist"]), W, H,
@@ -244,9 +251,10 @@ class Av1GpuEngine:
         info = (ws["iy"], ws["iu"], ws["iv"])
         _ok(lib.tv_av1e_lfinfo(_p(mode), W, H, B, _p(lvl), *map(_p, info), st))
         # every transform / block edge of the encoder's planes is on the 16 (luma) / 8
-        # (chroma) grid: blocks are 16x16 or merged 32 / 64 with one TX per plane
+        # (chroma) grid: blocks are 16x16 or merged 32 / 64 with one TX per plane; the luma of a
+        # transform-split block has 8x8 transforms
         for c in range(3):
-            ops.deblock(rec[c], info[c], c > 0, 0, estep=8 if c else 16, out=dbk[c])
+            ops.deblock(rec[c], info[c], c > 0, 0, estep=8 if c or self.tx_split else 16, out=dbk[c])
         dirs, var = ops.cdef_dirs(dbk[0], out=(ws["dirs"], ws["var"]))
         _ok(lib.tv_av1e_cdef_skip(_p(mode), _p(dirs), W, H, B, st))  # skip blocks are not filtered
         se = [ops.cdef_search(src[c], dbk[c], dirs, var, c > 0, dmp, luma_w8=W // 8,
@@ -336,7 +344,8 @@ class Av1GpuEngine:
             outs = []
             for p, k in enumerate(("ly", "lu", "lv")):
                 o = torch.empty(max(1, totals[p]), dtype=torch.int16, device=self.dev)
-                _ok(lib.tv_av1e_tb_pack(_p(S[k]), _p(lens[p]), _p(ends[p]), ntb, nb, nseg, Bmax, p, _p(o), st))
+                _ok(lib.tv_av1e_tb_pack(_p(S[k]), _p(S["mode"]), _p(lens[p]), _p(ends[p]), ntb, nb, nseg, Bmax, p, _p(o),
+                                        st))
                 outs.append((o, (ends[p] - lens[p]).view(F, nseg, nb)[:, :, 0]))
             host = GopHost(
                 nframes=F,
@@ -363,7 +372,8 @@ class Av1GpuEngine:
         for t in range(g.nframes):
             tabs = g.tabs[t, b]
             q = int(g.qm[t, b])
-            fp = av1m.frame_params(g.key[t], q, [int(LF_LEVEL[q])] * 4, 0, self.damping, tabs[:8], tabs[8:])
+            fp = av1m.frame_params(g.key[t], q, [int(LF_LEVEL[q])] * 4, 0, self.damping, tabs[:8], tabs[8:],
+                                   tx_select=self.tx_split)
             lev = [pk[0][pk[1][t, b]:] for pk in g.packed]  # eob-truncated scan-order TBs
             tus.append(wr.write(fp, np.ascontiguousarray(g.mode[t, b]), np.ascontiguousarray(g.mv[t, b]), lev[0],
                                 lev[1], lev[2], np.ascontiguousarray(g.fbidx[t, b]), packed=2, seq_header=g.key[t],

@@ -99,12 +99,13 @@ class CpuAv1Engine:
 
     def __init__(self, width: int, height: int, batch: int, qindex: int = 100, threads: int | None = None, seed: int = 1,
                  cascade: bool = True, intra_in_inter: bool = False, cfl: bool = False, dir_intra: bool = False,
-                 **_):
+                 tx_split: bool = False, **_):
         self.w, self.h, self.B, self.q, self.seed = width, height, batch, int(qindex), seed
         self.cascade = cascade
         self.intra_in_inter = bool(intra_in_inter)
         self.cfl = bool(cfl)
         self.dir_intra = bool(dir_intra)
+        self.tx_split = bool(tx_split)
         self.W, self.H = av1m.coded_size(width, height)
         self.pool = cf.ThreadPoolExecutor(threads or 2)
         self.lr_enabled = True
@@ -112,7 +113,8 @@ class CpuAv1Engine:
     def _one(self, start: int, n: int, qm):
         frames = [hevc.synth_frame(self.seed, start + t, self.w, self.h) for t in range(n)]
         r = av1m.golden_encode(frames, self.w, self.h, self.q, qmap=qm, cascade=self.cascade,
-                               intra_in_inter=self.intra_in_inter, cfl=self.cfl, dir_intra=self.dir_intra)
+                               intra_in_inter=self.intra_in_inter, cfl=self.cfl, dir_intra=self.dir_intra,
+                               tx_split=self.tx_split)
         tus = av1m.split_temporal_units(r.stream, r.tu_sizes)
         W, H = self.W, self.H
         sse = []

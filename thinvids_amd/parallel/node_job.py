@@ -1085,6 +1085,8 @@ def main(argv=None) -> int:
                     help="AV1: chroma from luma in intra blocks (off by default)")
     ap.add_argument("--av1-dir-intra", dest="dir_intra", action="store_true",
                     help="AV1: directional intra angles with CDF-based mode rates (off by default)")
+    ap.add_argument("--av1-tx-split", dest="tx_split", action="store_true",
+                    help="AV1: 8x8 transform split of the luma of inter blocks (off by default)")
     ap.add_argument("--deinterlace", action="store_true", help="bwdif every segment (DVD-native interlaced sources)")
     a = ap.parse_args(argv)
     import torch
@@ -1108,7 +1110,8 @@ def main(argv=None) -> int:
                          **({"sign_hiding": True} if a.sign_hiding else {}),
                          **({"intra_in_inter": True} if a.intra_in_inter else {}),
                          **({"cfl": True} if a.cfl else {}),
-                         **({"dir_intra": True} if a.dir_intra else {})},
+                         **({"dir_intra": True} if a.dir_intra else {}),
+                         **({"tx_split": True} if a.tx_split else {})},
                   deinterlace=a.deinterlace)
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res), flush=True)

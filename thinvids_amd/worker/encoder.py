@@ -59,6 +59,7 @@ class EncodeSpec:
     intra_in_inter: bool = False  # AV1: 16x16 intra blocks in inter frames (tv/av1_enc.h)
     cfl: bool = False  # AV1: chroma from luma in intra blocks (tv/av1_enc.h)
     dir_intra: bool = False  # AV1: directional intra angles with CDF-based mode rates (tv/av1_enc.h)
+    tx_split: bool = False  # AV1: 8x8 transform split of the luma of inter blocks (tv/av1_enc.h)
     # where the WPP substreams are CABAC-coded ("auto" / "gpu" / "host"): the same bytes, so
     # not a coding tool (not in tools() / the checkpoint fingerprint), but its own engine
     entropy: str = "auto"
@@ -66,7 +67,7 @@ class EncodeSpec:
     def engine_key(self):
         if self.codec == "av1":
             return ("av1", self.width, self.height, self.av1_qindex(), self.cascade, self.intra_in_inter, self.cfl,
-                    self.dir_intra)
+                    self.dir_intra, self.tx_split)
         return (self.width, self.height, self.qp, self.gop, self.search_range, self.deblock, self.sao, self.seed,
                 self.crf, self.hevc_bframes(), self.wpp, self.rqt, self.pintra, self.cascade, self.rdoq, self.entropy, self.subpel_satd,
                 self.sign_hiding)
@@ -84,6 +85,8 @@ class EncodeSpec:
             t["cfl"] = True
         if self.dir_intra and self.codec == "av1":
             t["dir_intra"] = True
+        if self.tx_split and self.codec == "av1":
+            t["tx_split"] = True
         return t
 
     def hevc_bframes(self) -> int:
@@ -215,7 +218,7 @@ class EngineCache:
 
             eng = Av1GpuEngine(spec.width, spec.height, batch=batch, qindex=spec.av1_qindex(), device=self.device,
                                cascade=spec.cascade, intra_in_inter=spec.intra_in_inter, cfl=spec.cfl,
-                               dir_intra=spec.dir_intra)
+                               dir_intra=spec.dir_intra, tx_split=spec.tx_split)
             eng.batch = eng.B
             return eng
         return GpuEngine(spec.width, spec.height, qp=spec.qp, batch=batch, gop=spec.gop, search_range=spec.search_range,
@@ -388,7 +391,7 @@ def _encode_cpu(frames, spec: EncodeSpec, st: PartStats | None, fq=None) -> byte
             qm = None if fq is None else [av1.qindex_for_hevc_qp(int(x)) for x in fq[a:a + spec.gop]]
             r = av1.golden_encode(frames[a:a + spec.gop], spec.width, spec.height, spec.av1_qindex(), qmap=qm,
                                   cascade=spec.cascade, intra_in_inter=spec.intra_in_inter, cfl=spec.cfl,
-                                  dir_intra=spec.dir_intra)
+                                  dir_intra=spec.dir_intra, tx_split=spec.tx_split)
             bs += r.stream
             for f in r.recon:
                 recons.append((f[:W * H].reshape(H, W), f[W * H:W * H * 5 // 4].reshape(H // 2, W // 2),

@@ -110,7 +110,8 @@ def encode_spec_for_job(job: dict, settings: dict | None = None) -> EncodeSpec:
                       sign_hiding=as_bool(job.get("sign_hiding") or s.get("tv_sign_hiding") or "0"),
                       intra_in_inter=as_bool(job.get("av1_intra_blocks") or s.get("tv_av1_intra_blocks") or "0"),
                       cfl=as_bool(job.get("av1_cfl") or s.get("tv_av1_cfl") or "0"),
-                      dir_intra=as_bool(job.get("av1_dir_intra") or s.get("tv_av1_dir_intra") or "0"))
+                      dir_intra=as_bool(job.get("av1_dir_intra") or s.get("tv_av1_dir_intra") or "0"),
+                      tx_split=as_bool(job.get("av1_tx_split") or s.get("tv_av1_tx_split") or "0"))
 
 
 def _pow2(n: int) -> int:

@@ -1,10 +1,12 @@
 """AV1 engine speed, bytes and PSNR with an opt-in intra tool off and on: chroma from luma (--name
-cfl, the default) or directional intra (--name dir_intra); both in tv/av1_enc.h.
+cfl, the default), directional intra (--name dir_intra) or the transform split (--name tx_split);
+all in tv/av1_enc.h.
 
     python tools/av1_cfl_speed.py [--res 1920x1080] [--qindex 100] [--gop 64] [--batch 8] [--textured]
                                   [--intra-in-inter] [--rounds 3] [--steps 2] [--warmup 1] [--out FILE]
     python tools/av1_cfl_speed.py --gop 2            # key-frame heavy: every second frame is a key frame
     python tools/av1_cfl_speed.py --name dir_intra   # the same for directional intra
+    python tools/av1_cfl_speed.py --name tx_split    # the same for the transform split
     python tools/av1_cfl_speed.py --tool on --once   # one untimed step of one engine, for a kernel profiler
 
 Both engines (tool off, tool on) live in this one process and take turns, off / on / off / on ...,
@@ -30,7 +32,7 @@ sys.path.insert(0, ROOT)
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--name", choices=("cfl", "dir_intra"), default="cfl", help="the tool that is switched")
+    ap.add_argument("--name", choices=("cfl", "dir_intra", "tx_split"), default="cfl", help="the tool that is switched")
     ap.add_argument("--res", default="1920x1080")
     ap.add_argument("--qindex", type=int, default=100)
     ap.add_argument("--gop", type=int, default=64, help="frames per segment (2: key-frame heavy; 64: the bench's GOP)")
@@ -78,6 +80,8 @@ def main() -> None:
     def tool_blocks(mode) -> int:
         if a.name == "cfl":
             return int(av1.mode_cfl(mode)[0].sum())
+        if a.name == "tx_split":
+            return int(av1.mode_tx(mode)[0].sum())
         _, yd, _, uvd = av1.mode_angles(mode)
         return int(((yd != 0) | (uvd != 0)).sum())
 
@@ -91,7 +95,8 @@ def main() -> None:
         ps = eng.psnr(g)
         return {"tool": state, "frames_per_s": round(a.steps * a.batch * a.gop / dt, 1),
                 "last_step_bytes": sum(len(s) for s in segs), "last_step_psnr": {k: round(v, 4) for k, v in ps.items()},
-                "last_step_cfl_blocks" if a.name == "cfl" else "last_step_angled_blocks": tool_blocks(g.mode),
+                {"cfl": "last_step_cfl_blocks", "tx_split": "last_step_split_blocks"}.get(
+                    a.name, "last_step_angled_blocks"): tool_blocks(g.mode),
                 "last_step_intra_blocks": int(((np.asarray(g.mode) & 1) == 0).sum())}
 
     try:

@@ -253,9 +253,11 @@ def rate_rows(rows, n) -> list:
 
 # Rate tables of the opt-in directional intra search (tv/av1_enc.h "directional intra"): the
 # default CDFs' symbol costs, emitted next to the CDFs they come from.  y_mode: size group 2
-# (16x16 blocks) only.
+# (16x16 blocks) only.  txfm_split: the flag's cost in the opt-in transform split decision
+# (tv/av1_enc.h "transform split").
 RATES = {"kf_y_mode": ((5, 5), lambda rows: rows), "y_mode": ((), lambda rows: rows[2:3]),
-         "uv_mode1": ((13,), lambda rows: rows), "angle_delta": ((8,), lambda rows: rows)}
+         "uv_mode1": ((13,), lambda rows: rows), "angle_delta": ((8,), lambda rows: rows),
+         "txfm_split": ((21,), lambda rows: rows)}
 
 
 def emit() -> str:

@@ -64,7 +64,7 @@ def run_point(args):
                 qm = [av1.qindex_for_hevc_qp(x) for x in fq[s0:s0 + n]]
             r = av1.golden_encode(frames[s0:s0 + a["gop"]], w, h, q, qmap=qm,
                                   intra_in_inter=a.get("intra_in_inter", False), cfl=a.get("cfl", False),
-                                  dir_intra=a.get("dir_intra", False))
+                                  dir_intra=a.get("dir_intra", False), tx_split=a.get("tx_split", False))
             stream += r.stream
             ys += [hevc.psnr(f[0], rec[:W * H].reshape(H, W)[:h, :w]) for f, rec in zip(frames[s0:], r.recon)]
             for f, rec in zip(frames[s0:], r.recon):  # chroma MSE for the 6:1:1 PSNR-YUV
@@ -134,6 +134,7 @@ def main():
     ap.add_argument("--intra-in-inter", type=int, default=0, help="av1: intra blocks in inter frames (tv/av1_enc.h)")
     ap.add_argument("--cfl", type=int, default=0, help="av1: chroma from luma (tv/av1_enc.h)")
     ap.add_argument("--dir-intra", type=int, default=0, help="av1: directional intra angles, CDF-based mode rates (tv/av1_enc.h)")
+    ap.add_argument("--tx-split", type=int, default=0, help="av1: 8x8 transform split of the luma of inter blocks (tv/av1_enc.h)")
     ap.add_argument("--fan", type=int, default=0, help="av1: replace the clip by the oriented-grating clip of tests/av1_dir_cases.py")
     ap.add_argument("--chroma-k", default="", help="KU,KV: replace the clip's chroma by one that follows its luma "
                     "(U = 128 + KU * (Y2x2 - 128) / 8 + noise; models/av1.py correlated_chroma)")
@@ -148,7 +149,7 @@ def main():
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
                ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
                sign_hiding=bool(a.sign_hiding), intra_in_inter=bool(a.intra_in_inter), cut=a.cut,
-               engine=a.engine, cfl=bool(a.cfl), dir_intra=bool(a.dir_intra), fan=bool(a.fan), chroma_k=[int(x) for x in a.chroma_k.split(",")] if a.chroma_k else [])
+               engine=a.engine, cfl=bool(a.cfl), dir_intra=bool(a.dir_intra), tx_split=bool(a.tx_split), fan=bool(a.fan), chroma_k=[int(x) for x in a.chroma_k.split(",")] if a.chroma_k else [])
     qps = [int(q) for q in a.qps.split(",")]
     if a.engine == "gpu":
         pts = [run_point((q, cfg)) for q in qps]
