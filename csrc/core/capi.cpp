@@ -10,6 +10,7 @@
 #include "tv/cpu_encoder.h"
 #include "tv/hevc_codec.h"
 #include "tv/me_model.h"
+#include "tv/rdq.h"
 #include "tv/sdh.h"
 #include "tv/synth.h"
 #include "tv/synth_tile.h"
@@ -481,6 +482,13 @@ void tv_sdh_deltas(const int* coef, int n, int qp, int log2N, int intra, int* re
     ref[i] = sdh_delta(coef[i], l, qp, log2N);
     fast[i] = sdh_delta_fast(coef[i], l, q);
   }
+}
+// rate-distortion quantisation (tv/rdq.h) of one inter TB: coef N x N row-major, c 0 luma / 1
+// chroma, lambda <= 0: kRdqLambda.  lev (N x N) receives the levels, J[3] the model's J after
+// each of the three stages.  Returns kRdqLambda.
+int tv_rdq_tb(const int* coef, int qp, int log2N, int c, int lambda, int16_t* lev, long long* J) {
+  rdq_tb(coef, qp, log2N, c, lev, 1 << log2N, J, lambda > 0 ? lambda : kRdqLambda);
+  return kRdqLambda;
 }
 int tv_demux_mp4(const uint8_t* mp4, size_t n, int* w, int* h, int* nframes, int* timescale,
                  int* delta, void* out) {

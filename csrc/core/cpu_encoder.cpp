@@ -20,6 +20,7 @@
 #include "tv/cpu_encoder.h"
 #include "tv/me_model.h"
 #include "tv/rc_model.h"
+#include "tv/rdq.h"
 #include "tv/sdh.h"
 
 namespace tv {
@@ -405,14 +406,20 @@ void analyze_inter_b(const SeqConfig& cfg, const Picture& src, const Picture& re
 // -------------------------------- reconstruction ----------------------------------------
 // Transform + quantise one TB of residual; writes levels into the plane; returns cbf.
 // sdh_scan >= 0: sign data hiding (tv/sdh.h) with that scan index for the TB's 4x4 groups.
-static int code_tb(const int* resid, int log2N, int qp, bool intra, int16_t* lev, int ls, int rdoq, int sdh_scan) {
+// rdq_c >= 0: rate-distortion quantisation (tv/rdq.h) of an inter TB of component class rdq_c,
+// in place of the dead zone and RDOQ-lite.
+static int code_tb(const int* resid, int log2N, int qp, bool intra, int16_t* lev, int ls, int rdoq, int sdh_scan, int rdq_c) {
   const int N = 1 << log2N;
   int coef[32 * 32];
   forward_transform(resid, log2N, coef);
   int nz = 0, sumabs = 0;
+  if (rdq_c >= 0 && !intra) {
+    rdq_tb(coef, qp, log2N, rdq_c, lev, ls);
+    rdoq = 0;
+  }
   for (int j = 0; j < N; ++j)
     for (int i = 0; i < N; ++i) {
-      const int l = quant_level(coef[j * N + i], qp, log2N, intra);
+      const int l = rdq_c >= 0 && !intra ? lev[j * ls + i] : quant_level(coef[j * N + i], qp, log2N, intra);
       lev[j * ls + i] = (int16_t)l;
       nz += l != 0;
       sumabs += tv_abs(l);
@@ -500,7 +507,7 @@ void reconstruct_frame(const SeqConfig& cfg, const Picture& src, const Picture* 
       int16_t* L = (c == 0 ? fd.coef_y : (c == 1 ? fd.coef_u : fd.coef_v)).data() + (size_t)y * stride + x;
       const int qq = c ? qpc : qp;
       const int cb = code_tb(resid, l2, qq, intra, L, stride, cfg.rdoq ? kRdoqMode : 0,
-                             cfg.sign_hiding ? scan_idx_for(intra, l2, c, fd.ipm[u]) : -1);
+                             cfg.sign_hiding ? scan_idx_for(intra, l2, c, fd.ipm[u]) : -1, cfg.rd_quant ? (c ? 1 : 0) : -1);
       cbf |= cb << c;
       recon_tb(L, stride, cb, l2, qq, pred, rec.plane(c) + (size_t)y * stride + x, stride);
     }

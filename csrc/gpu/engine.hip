@@ -276,6 +276,7 @@ class Core {
     g_.rdoq = seq_.rdoq ? kRdoqMode : 0;
     g_.subpel_satd = seq_.subpel_satd ? 1 : 0;
     g_.sign_hiding = seq_.sign_hiding ? 1 : 0;
+    g_.rd_quant = seq_.rd_quant ? 1 : 0;
     seq_.mgop = c.mgop;
     if (c.mgop > 1) {
       const GopPlan gp = plan_gop(2 * c.mgop + 1, c.mgop);

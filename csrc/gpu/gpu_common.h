@@ -24,6 +24,7 @@ struct Geo {
   int rdoq = 0;    // k_inter_recon RDOQ-lite mode (hevc_defs.h kRdoqMode; 0 off): SeqConfig::rdoq
   int subpel_satd = 0;  // k_inter_me<true>: SATD sub-pel decision (tv/me_model.h); SeqConfig::subpel_satd
   int sign_hiding = 0;  // k_inter_recon<true> / k_intra_recon<true> / k_pintra_recon<true>: sign data hiding (tv/sdh.h)
+  int rd_quant = 0;     // k_inter_recon<.., true>: rate-distortion quantisation of inter TBs (tv/rdq.h)
 };
 
 inline Geo make_geo(int dw, int dh) {

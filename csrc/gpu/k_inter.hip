@@ -24,6 +24,7 @@
 #include "wave_tb.h"
 #include "tv/me_model.h"
 #include "tv/rc_model.h"
+#include "tv/rdq.h"
 #include "tv/sdh.h"
 
 namespace tv {
@@ -1018,6 +1019,8 @@ __constant__ TbFragTables kTbFragDev = make_tb_frag();
 
 struct PReconLds {
   alignas(16) TbFragTables F;  // the constant operands as f16 fragments (tv/tb_frag.h)
+  // (between stage 2 and stage 3 both are dead: the rd_quant pass keeps its per-coefficient level drops
+  // in tmpYh and its per-group costs in tmpYl)
   alignas(16) _Float16 tmpYh[32 * kTmpYP], tmpYl[32 * kTmpYP];        // stage 1 / stage 3 outputs (luma), v = 256 hi + lo
   alignas(16) _Float16 tmpCh[2][16 * kTmpCP], tmpCl[2][16 * kTmpCP];  // the same for Cb, Cr
   int16_t resY[32 * 32];      // residual, later levels (luma)
@@ -1032,7 +1035,7 @@ struct PReconLds {
       uint8_t bwin[4][15 * 16];   // per wave: 15x15 luma reference window of a bi unit
       int16_t bh[4][15 * 8];      // per wave: horizontal filter pass (15 rows x 8)
     };
-    // k_inter_recon<true> (sign data hiding), written by stage 2 when the prediction buffers
+    // k_inter_recon<true, ..> (sign data hiding) and <.., true> (rd_quant), written by stage 2 when the prediction buffers
     // above are dead: per coefficient sdh_delta + 64 as a byte (inter rounding: -64 <= d < 192;
     // luma 32x32, Cb 16x16, Cr 16x16), and per lane's four coefficients of a row the bits
     // "coefficient r < 0" (a zero level takes its sign from there)
@@ -1077,7 +1080,10 @@ __device__ __forceinline__ bool pr_zeroed(const PReconLds& L, int id) {
 // kSdh (SeqConfig::sign_hiding, tv/sdh.h): stage 2 also keeps every coefficient's distance
 // from its level, and a pass after RDOQ-lite adjusts one level of each coefficient group whose
 // parity does not carry its hidden sign.  <false> compiles none of it.
-template <bool kSdh>
+// kRdq (SeqConfig::rd_quant, tv/rdq.h): stage 2 keeps the distances as for kSdh, and a pass in
+// the place of RDOQ-lite chooses the levels by rate-distortion cost, one thread per coefficient
+// group.  <.., false> compiles none of it.
+template <bool kSdh, bool kRdq>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) k_inter_recon(FrameSet src, FrameSet ref, const uint8_t* phase,
                                                      FrameSet rec, DecisionSet dec, Geo g,
                                                      FrameSet ref1, const uint8_t* phase1) {
@@ -1366,7 +1372,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
   // TBs are 4-aligned, so the levels are one 8-byte store, the TB statistics one pair of LDS
   // atomics per lane, and only the first column can be the TB's origin.  multi: some TB has
   // >= 2 levels -- this lane adds two, or finds the count already non-zero.
-  // kSdh: di = the lane's first coefficient in sdh_d (luma y * 32 + x, chroma 1024 + 256 pl + y * 16 + x)
+  // kSdh / kRdq: di = the lane's first coefficient in sdh_d (luma y * 32 + x, chroma 1024 + 256 pl + y * 16 + x)
   auto emit_levels = [&](int16_t* dst, int id, int sh2, const QuantParams& q, const int* v, bool origin, int di) {
     int cnt = 0, sum = 0, lev[4];
     uint32_t dd = 0, neg = 0;
@@ -1376,12 +1382,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
       lev[r] = quant_fast(cf, q);
       cnt += lev[r] != 0;
       sum += tv_abs(lev[r]);
-      if constexpr (kSdh) {
+      if constexpr (kSdh || kRdq) {
         dd |= (uint32_t)(sdh_delta_fast(cf, lev[r], q) + 64) << (8 * r);
         neg |= (cf < 0 ? 1u : 0u) << r;
       }
     }
-    if constexpr (kSdh) {
+    if constexpr (kSdh || kRdq) {
       *reinterpret_cast<uint32_t*>(&L.sdh_d[di]) = dd;
       L.sdh_neg[di >> 2] = (uint8_t)neg;
     }
@@ -1410,13 +1416,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
       const QuantParams qy = quant_params(qp, l2);
       const int m = (1 << l2) - 1, y = (t >> 1) * 16 + fi, x = (t & 1) * 16 + kq * 4;
       const int id = whole ? 0 : 4 * t + (l2 == 3 ? (fi >> 3) * 2 + (kq >> 1) : 0);
-      emit_levels(&L.resY[y * 32 + x], id, l2 + 6, qy, o, (x & m) == 0 && (y & m) == 0, kSdh ? y * 32 + x : 0);
+      emit_levels(&L.resY[y * 32 + x], id, l2 + 6, qy, o, (x & m) == 0 && (y & m) == 0, kSdh || kRdq ? y * 32 + x : 0);
     } else if (whole) {
       const int pl = t - 4;
       const int ia = fi * kTmpCP + 4 * kq;
       frag_tile_split_a(frag4(&L.tmpCh[pl][ia]), frag4(&L.tmpCl[pl][ia]), C16(4, 0), o);
       emit_levels(&L.resC[pl][fi * 16 + kq * 4], 16 + 16 * pl, 10, quant_params(qpc, 4), o, lane == 0,
-                  kSdh ? 1024 + 256 * pl + fi * 16 + kq * 4 : 0);
+                  kSdh || kRdq ? 1024 + 256 * pl + fi * 16 + kq * 4 : 0);
     } else {
       const int q = t - 4, ox = (q & 1) * 8, oy = (q >> 1) * 8, l2 = L.qtype[q] == 1 ? 3 : 2;
       // A(r = fi, k = 4 kq ..): inside plane fi >> 3's block iff pin; the read is in bounds either way
@@ -1428,7 +1434,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
         const int m = (1 << l2) - 1, pl = fi >> 3, y = oy + (fi & 7), x = ox + 4 * (kq & 1);
         const int id = 16 + 16 * pl + 4 * q + (l2 == 2 ? ((fi >> 2) & 1) * 2 + (kq & 1) : 0);
         emit_levels(&L.resC[pl][y * 16 + x], id, l2 + 6, qc, o, (x & m) == 0 && (y & m) == 0,
-                    kSdh ? 1024 + 256 * pl + y * 16 + x : 0);
+                    kSdh || kRdq ? 1024 + 256 * pl + y * 16 + x : 0);
       }
     }
   }
@@ -1441,7 +1447,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
   // per TB) and its diagonal is >= rdoq_dmin.  One thread per 4x4 group (luma 64, Cb / Cr 16).
   // A CTB whose TBs hold at most one level each skips it (workgroup-uniform): a lone level
   // the pass could drop is dropped by the whole-TB rule (pr_zeroed) anyway.
-  if (rdoq && L.multi) {
+  if (!kRdq && rdoq && L.multi) {
     int code = 0, key = 0, id = 0, dmin = 1 << 20;
     int16_t* p = nullptr;
     int st = 32;
@@ -1488,6 +1494,112 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
     }
     __syncthreads();
   }
+  // ---- rate-distortion quantisation (tv/rdq.h) in the place of RDOQ-lite: one thread per 4x4
+  // group runs stages 1 and 2 on its sixteen coefficients (rdq_group: the levels it changes go
+  // straight back into the level plane), stage 3 is a sum and a minimum over the TB's groups
+  // in coding order.  All groups of a TB are in one wave (luma wave 0, chroma wave 1), so the
+  // per-group values cross lanes through LDS with wave fences only; they live in the f16
+  // images, dead between stage 2 and stage 3.  The TB statistics follow the levels.
+  // kSdh: the sign-hiding pass needs the distance from the final level, d + 256 (|l0| - |l|);
+  // |l0| - |l| + 1 (0..4) per coefficient is kept as a byte beside d, in tmpYh.
+  if constexpr (kRdq) {
+    int* gf = reinterpret_cast<int*>(L.tmpYl);  // [96] stage-2 J of the group at TB slot + rank
+    int* je = gf + 96;                          // [96] J of ending the TB in that group
+    uint8_t* drop = reinterpret_cast<uint8_t*>(L.tmpYh);
+    static_assert(sizeof(L.tmpYl) >= 2 * 96 * sizeof(int) && sizeof(L.tmpYh) >= sizeof(L.sdh_d), "rdq scratch fits the f16 images");
+    if (wave < 2) {
+      int x, y, l2, pl = -1, id, st, di, base, q;
+      int16_t* p;
+      if (tid < 64) {
+        x = (tid & 7) * 4, y = (tid >> 3) * 4;
+        l2 = pr_l2_luma(L, x, y);
+        id = pr_tb_luma(L, x, y);
+        p = &L.resY[y * 32 + x], st = 32, di = y * 32 + x, base = 4 * id;
+        q = (y >> 4) * 2 + (x >> 4);
+      } else {
+        const int c = (tid - 64) & 31;
+        pl = c >> 4, x = (c & 3) * 4, y = ((c & 15) >> 2) * 4;
+        l2 = pr_l2_luma(L, 2 * x, 2 * y) - 1;
+        id = pr_tb_chroma(L, pl, x, y);
+        p = &L.resC[pl][y * 16 + x], st = 16, di = 1024 + 256 * pl + y * 16 + x, base = 64 + id - 16;
+        q = (y >> 3) * 2 + (x >> 3);
+      }
+      // a quadrant that is an intra CU keeps its levels: k_pintra_recon codes it again, whole
+      const bool act = tid < 96 && !L.qintra[L.qtype[0] == 0 ? 0 : q];
+      const int s = 1 << (l2 - 2), m = (1 << l2) - 1, gx = (x & m) >> 2, gy = (y & m) >> 2, rank = rdq_rank(gx, gy, s);
+      auto at = [&](int n) {
+        const int sp = sdh_scan_pos(0, n);
+        return (sp >> 2) * st + (sp & 3);
+      };
+      auto stats = [&](int& cnt, int& sum) {
+        cnt = sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint2 w = *reinterpret_cast<const uint2*>(p + j * st);
+          const int a = (int)(int16_t)(w.x & 0xffff), b = (int)(int16_t)(w.x >> 16), c = (int)(int16_t)(w.y & 0xffff), d = (int)(int16_t)(w.y >> 16);
+          cnt += (a != 0) + (b != 0) + (c != 0) + (d != 0);
+          sum += tv_abs(a) + tv_abs(b) + tv_abs(c) + tv_abs(d);
+        }
+      };
+      int cnt0, sum0;
+      stats(cnt0, sum0);
+      const unsigned long long any = __ballot(act && cnt0 != 0);  // the wave's non-empty groups
+      const int nb = tid < 64 ? 8 : 4;                           // lanes to the group below
+      const int right = gx + 1 < s ? (int)((any >> ((lane + 1) & 63)) & 1) : 0;
+      const int below = gy + 1 < s ? (int)((any >> ((lane + nb) & 63)) & 1) : 0;
+      if constexpr (kSdh) {  // |l0| - |l| + 1 per coefficient: 1 until a level moves
+        if (tid < 96) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) *reinterpret_cast<uint32_t*>(&drop[di + j * st]) = 0x01010101u;
+        }
+      }
+      RdqGroup g{};
+      if (act) {
+        g = rdq_group([&](int n) { return tv_abs((int)p[at(n)]); }, [&](int n) { return (int)L.sdh_d[di + at(n)] - 64; },
+                      [&](int n, int a) {
+                        const int o = at(n), l = p[o];  // l != 0: a zero stays zero
+                        if constexpr (kSdh) drop[di + o] = (uint8_t)(1 + tv_abs(l) - a);
+                        p[o] = (int16_t)(l < 0 ? -a : a);
+                      },
+                      pl >= 0 ? 1 : 0, rank == 0, right, below, kRdqLambda);
+        if (g.maxmag > 2) atomicMax(&L.cgmax[id], rank);  // the TB cannot end before this group
+        gf[base + rank] = g.gfull;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (act) {
+        int before = 0;
+        for (int j = 0; j < rank; ++j) before += gf[base + j];
+        const bool valid = (g.nlast >= 0 || rank == 0) && rank >= L.cgmax[id];
+        je[base + rank] = valid ? rdq_end_cost(g, before, pl >= 0 ? 1 : 0, gx + gy, kRdqLambda) : 0x7fffffff;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (act) {
+        int best = 0x7fffffff, k = 0;
+        for (int j = 0; j < s * s; ++j) {
+          const int e = je[base + j];
+          if (e <= best) best = e, k = j;
+        }
+        const int keep = rank > k ? -1 : (rank == k ? g.nlast : (g.emptied ? -1 : 15));  // last scan position kept
+        for (int n = keep + 1; n < 16; ++n) {
+          const int o = at(n), a = tv_abs((int)p[o]);
+          if (a) {
+            if constexpr (kSdh) drop[di + o] = (uint8_t)(drop[di + o] + a);
+            p[o] = 0;
+          }
+        }
+        int cnt1, sum1;
+        stats(cnt1, sum1);
+        if (cnt1 != cnt0) atomicAdd(&L.nz[id], cnt1 - cnt0);
+        if (sum1 != sum0) atomicAdd(&L.sa[id], sum1 - sum0);
+        if (rank == 0) L.dc[id] = p[0];
+      }
+    }
+    __syncthreads();
+  }
   // ---- sign data hiding (tv/sdh.h) on the final levels: after RDOQ-lite, only in TBs the
   // lone-level rule keeps, and without touching nz / sa / dc -- a TB that now looks like a lone
   // +-1 stays.  One thread per 4x4 group as above; inter TBs scan diagonally.  (A quadrant that
@@ -1511,7 +1623,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))
           return (s >> 2) * st + (s & 3);
         };
         int pos, value;
-        if (sdh_adjust([&](int n) { return (int)p[at(n)]; }, [&](int n) { return (int)L.sdh_d[di + at(n)] - 64; },
+        // kRdq: the distance from the final level (the pass above left |l0| - |l| + 1 in tmpYh)
+        if (sdh_adjust([&](int n) { return (int)p[at(n)]; },
+                       [&](int n) {
+                         int d = (int)L.sdh_d[di + at(n)] - 64;
+                         if constexpr (kRdq) d += 256 * ((int)reinterpret_cast<const uint8_t*>(L.tmpYh)[di + at(n)] - 1);
+                         return d;
+                       },
                        [&](int n) { const int a = di + at(n); return ((L.sdh_neg[a >> 2] >> (a & 3)) & 1) != 0; }, pos, value))
           p[at(pos)] = (int16_t)value;
       }
@@ -1705,6 +1823,12 @@ void launch_rc_crf(const uint8_t* q, const int* ccost, int8_t* qp, const Geo& g,
   k_rc_crf<<<B, 256, 0, s>>>(q, ccost, qp, g, crf, intra ? 1 : 0);
 }
 
+// the instantiation SeqConfig::sign_hiding / rd_quant select
+static auto inter_recon_kernel(const Geo& g) {
+  if (g.rd_quant) return g.sign_hiding ? k_inter_recon<true, true> : k_inter_recon<false, true>;
+  return g.sign_hiding ? k_inter_recon<true, false> : k_inter_recon<false, false>;
+}
+
 void launch_inter_frame(FrameSet src, FrameSet ref, const uint8_t* phase, FrameSet rec, DecisionSet dec,
                         const Geo& g, const RcTables* rc, int range, const MeBuffers& me, int B, hipStream_t s,
                         const PIntraBuffers* pi) {
@@ -1713,7 +1837,7 @@ void launch_inter_frame(FrameSet src, FrameSet ref, const uint8_t* phase, FrameS
   const dim3 grid(g.wc * g.hc, B);
   (g.subpel_satd ? k_inter_me<true> : k_inter_me<false>)<<<grid, kMeThreads, 0, s>>>(src, ref, phase, dec, me.prev_mv, me.cmv, g, rc, range, nullptr, pi ? *pi : none);
   if (pi) launch_pintra_decide(src, dec, g, rc, *pi, B, s);
-  (g.sign_hiding ? k_inter_recon<true> : k_inter_recon<false>)<<<grid, 256, 0, s>>>(src, ref, phase, rec, dec, g, FrameSet{}, nullptr);
+  inter_recon_kernel(g)<<<grid, 256, 0, s>>>(src, ref, phase, rec, dec, g, FrameSet{}, nullptr);
   if (pi) launch_pintra_recon(src, rec, dec, g, *pi, B, s);
 }
 
@@ -1727,7 +1851,7 @@ void launch_inter_frame_b(FrameSet src, FrameSet ref0, const uint8_t* phase0, Fr
   k_me<<<grid, kMeThreads, 0, s>>>(src, ref0, phase0, dec, me0.prev_mv, me0.cmv, g, rc, range[0], meout, none);
   k_me<<<grid, kMeThreads, 0, s>>>(src, ref1, phase1, dec, me1.prev_mv, me1.cmv, g, rc, range[1], o1, none);
   k_bi_decide<<<grid, 256, 0, s>>>(src, phase0, phase1, meout, o1, dec, g, rc);
-  (g.sign_hiding ? k_inter_recon<true> : k_inter_recon<false>)<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, ref1, phase1);
+  inter_recon_kernel(g)<<<grid, 256, 0, s>>>(src, ref0, phase0, rec, dec, g, ref1, phase1);
 }
 
 }  // namespace gpu

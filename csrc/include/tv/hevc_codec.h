@@ -22,6 +22,7 @@
 #include "gop.h"
 #include "hevc_defs.h"
 #include "hevc_mvpred.h"
+#include "rdq.h"
 
 namespace tv {
 
@@ -69,6 +70,9 @@ struct SeqConfig {
   // sign data hiding (sign_data_hiding_enabled_flag; tv/sdh.h): the sign of the first level of a
   // coefficient group is carried by the parity of its magnitudes; off by default
   bool sign_hiding = false;
+  // rate-distortion quantisation of inter TBs (tv/rdq.h) in place of the dead zone and
+  // RDOQ-lite; off by default.  Its bit, kToolRdQuant = 1024, is declared with the model.
+  bool rd_quant = false;
   // All of these change the bitstream: they are explicit configuration (the C API's flag bits 3 / 4,
   // EncodeSpec.rqt / .pintra, part of the engine key and the checkpoint fingerprint), never
   // read from the environment here.
@@ -83,6 +87,7 @@ struct SeqConfig {
     rdoq = !(f & kFlagNoRdoq);
     subpel_satd = (f & kFlagSubpelSatd) != 0;
     sign_hiding = (f & kFlagSignHiding) != 0;
+    rd_quant = (f & kToolRdQuant) != 0;
   }
   int fps_num = 30, fps_den = 1;
   void finalize() {

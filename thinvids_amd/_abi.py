@@ -57,6 +57,7 @@ CORE = {
     "tv_tb_frag_expand": (i, [i, i32p]),
     "tv_quant_levels": (None, [i32p, i, i, i, i32p, i32p]),
     "tv_sdh_deltas": (None, [i32p, i, i, i, i, i32p, i32p]),
+    "tv_rdq_tb": (i, [i32p, i, i, i, i, i16p, llp]),
     "tv_hevc_spec_table": (i, [cstr, i32p, i]),
     # HEVC decoder
     "tv_decoder_new": (vp, []),

@@ -38,10 +38,10 @@ class CpuHevcEngine:
     def __init__(self, width: int, height: int, qp: int = 27, batch: int = 2, gop: int = 8, search_range: int = 16,
                  sao: bool = False, seed: int = 1, threads: int | None = None, bframes: int = 1, wpp: bool = True,
                  rqt: bool = True, pintra: bool = True, cascade: bool = True, rdoq: bool = True,
-                 subpel_satd: bool = False, sign_hiding: bool = False, **_):
+                 subpel_satd: bool = False, sign_hiding: bool = False, rd_quant: bool = False, **_):
         self.width, self.height, self.qp, self.batch, self.gop = width, height, qp, batch, gop
         self.tools = {"wpp": wpp, "rqt": rqt, "pintra": pintra, "cascade": cascade, "rdoq": rdoq,
-                      "subpel_satd": subpel_satd, "sign_hiding": sign_hiding}
+                      "subpel_satd": subpel_satd, "sign_hiding": sign_hiding, "rd_quant": rd_quant}
         self.search_range, self.sao, self.seed, self.bframes = search_range, sao, seed, int(bframes)
         self.threads = threads or 2
         self.pool = cf.ThreadPoolExecutor(self.threads)

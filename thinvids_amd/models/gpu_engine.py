@@ -57,7 +57,8 @@ class GpuEngine:
                  threads: int | None = None,
                  device: int = 0, max_merge: int = 5, crf: int = 0, bframes: int = 1, wpp: bool = True,
                  rqt: bool = True, pintra: bool = True, entropy: str | None = None, cascade: bool = True,
-                 rdoq: bool = True, subpel_satd: bool = False, sign_hiding: bool = False):
+                 rdoq: bool = True, subpel_satd: bool = False, sign_hiding: bool = False,
+                 rd_quant: bool = False):
         """`bframes` > 1: hierarchical-B mini-GOPs of that size (power of 2, tv/gop.h); the
         segments' streams are then in coding order (the decoder reorders by POC) and
         :meth:`last_recon` returns the last DISPLAY frame.
@@ -69,7 +70,8 @@ class GpuEngine:
         wpp=False always codes on the host.  `subpel_satd` (off by default): half- / quarter-pel
         vectors chosen by Hadamard SATD + MV rate (tv/me_model.h; k_inter_me<true>).
         `sign_hiding` (off by default): sign data hiding (tv/sdh.h; k_inter_recon<true>, the
-        intra recon kernels and the device CABAC coder)."""
+        intra recon kernels and the device CABAC coder).  `rd_quant` (off by default):
+        rate-distortion quantisation of inter TBs (tv/rdq.h; k_inter_recon<.., true>)."""
         self.lib = gpu_lib()
         self.width, self.height, self.qp = width, height, qp
         self.batch, self.gop = batch, gop
@@ -79,7 +81,7 @@ class GpuEngine:
         self.device = device
         self.bframes = int(bframes)
         self.entropy = resolve_entropy(entropy) if wpp else "host"
-        self.flags = (codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding)
+        self.flags = (codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding, rd_quant)
                       | (FLAG_HOST_ENTROPY if self.entropy == "host" else 0))
         self.h = self.lib.tv_engine_new_b(width, height, qp, batch, gop, search_range, self.flags,
                                           seed & 0xFFFFFFFF, self.threads, device, max_merge, int(crf), self.bframes)
@@ -236,12 +238,12 @@ def resolve_entropy(entropy: str | None = None) -> str:
 def estimate_footprint(width: int, height: int, batch: int, gop: int, sao: bool = False, bframes: int = 1,
                        wpp: bool = True, rqt: bool = True, pintra: bool = True, entropy: str | None = None,
                        cascade: bool = True, rdoq: bool = True, subpel_satd: bool = False,
-                       sign_hiding: bool = False) -> dict:
+                       sign_hiding: bool = False, rd_quant: bool = False) -> dict:
     """HBM / pinned-host bytes an engine of this geometry would allocate, computed by the
     native constructor's own size formulas without allocating (tv_engine_estimate)."""
     lib = gpu_lib()
     ent = resolve_entropy(entropy) if wpp else "host"
-    flags = codec_flags(True, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding)
+    flags = codec_flags(True, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding, rd_quant)
     flags |= FLAG_HOST_ENTROPY if ent == "host" else 0
     d, h = C.c_ulonglong(), C.c_ulonglong()
     ok(lib.tv_engine_estimate(width, height, batch, gop, flags, int(bframes), C.byref(d), C.byref(h)),

@@ -65,14 +65,19 @@ FLAG_CASCADE = 64  # the constant-QP I P P P QP cascade (tv/gop.h ippp_qp_offset
 FLAG_NO_RDOQ = 128  # no RDOQ-lite coefficient-group trimming (tv/hevc_defs.h kRdoqMode)
 FLAG_SUBPEL_SATD = 256  # half- / quarter-pel vectors chosen by SATD + MV rate (tv/me_model.h)
 FLAG_SIGN_HIDING = 512  # sign data hiding (tv/sdh.h)
+# a coding tool's bit that is declared with its model, not in hevc_codec.h: kToolRdQuant of
+# csrc/include/tv/rdq.h (tests/test_rd_quant.py compares the two)
+TOOL_RD_QUANT = 1024  # rate-distortion quantisation of inter TBs (tv/rdq.h)
 
 
 def codec_flags(deblock: bool = True, sao: bool = False, wpp: bool = True, rqt: bool = True, pintra: bool = True,
-                cascade: bool = False, rdoq: bool = True, subpel_satd: bool = False, sign_hiding: bool = False) -> int:
+                cascade: bool = False, rdoq: bool = True, subpel_satd: bool = False, sign_hiding: bool = False,
+                rd_quant: bool = False) -> int:
     """The native APIs' configuration word (tv::SeqConfig::set_flags) from the tools' switches;
-    SATD sub-pel and sign data hiding are off by default."""
+    SATD sub-pel, sign data hiding and rate-distortion quantisation are off by default."""
     on = {FLAG_DEBLOCK: deblock, FLAG_SAO: sao, FLAG_WPP: wpp, FLAG_NO_RQT: not rqt, FLAG_NO_PINTRA: not pintra,
-          FLAG_CASCADE: cascade, FLAG_NO_RDOQ: not rdoq, FLAG_SUBPEL_SATD: subpel_satd, FLAG_SIGN_HIDING: sign_hiding}
+          FLAG_CASCADE: cascade, FLAG_NO_RDOQ: not rdoq, FLAG_SUBPEL_SATD: subpel_satd, FLAG_SIGN_HIDING: sign_hiding,
+          TOOL_RD_QUANT: rd_quant}
     return sum(bit for bit, v in on.items() if v)
 
 
@@ -92,20 +97,21 @@ class CpuEncoder:
     def __init__(self, width: int, height: int, qp: int = 27, deblock: bool = True,
                  search_range: int = 64, max_merge: int = 5, sao: bool = False, crf: int = 0, wpp: bool = True,
                  bframes: int = 1, rqt: bool = True, pintra: bool = True, cascade: bool = True, rdoq: bool = True,
-                 subpel_satd: bool = False, sign_hiding: bool = False):
+                 subpel_satd: bool = False, sign_hiding: bool = False, rd_quant: bool = False):
         """`wpp`: one CABAC substream per CTB row (entropy_coding_sync; the GPU engine's
         default, it codes them on the device); `rqt` / `pintra` / `rdoq`: residual quadtree for
         inter CUs, intra 16x16 CUs in P pictures, trailing lone-level coefficient groups of inter
         TBs dropped; `subpel_satd`: sub-pel motion vectors chosen by Hadamard SATD instead of SAD,
-        off by default; `sign_hiding`: sign data hiding (tv/sdh.h), off by default (coding tools;
-        part of the bitstream identity)."""
+        off by default; `sign_hiding`: sign data hiding (tv/sdh.h), off by default; `rd_quant`:
+        rate-distortion quantisation of inter TBs (tv/rdq.h) in place of the dead zone and
+        RDOQ-lite, off by default (coding tools; part of the bitstream identity)."""
         if width % 2 or height % 2:
             raise ValueError("width/height must be even")
         self.lib = core_lib()
         self.width, self.height, self.qp = width, height, qp
         self.cw, self.ch = coded_size(width, height)
         self.bframes = int(bframes)
-        flags = codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding)
+        flags = codec_flags(deblock, sao, wpp, rqt, pintra, cascade, rdoq, subpel_satd, sign_hiding, rd_quant)
         if self.bframes > 1:
             if crf:
                 raise ValueError("CRF with B frames is not supported by the golden encoder")

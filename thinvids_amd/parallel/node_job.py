@@ -1079,6 +1079,8 @@ def main(argv=None) -> int:
                     help="HEVC: sub-pel motion vectors chosen by SATD + MV rate (off by default)")
     ap.add_argument("--sign-hiding", dest="sign_hiding", action="store_true",
                     help="HEVC: sign data hiding (off by default)")
+    ap.add_argument("--rd-quant", dest="rd_quant", action="store_true",
+                    help="HEVC: rate-distortion quantisation of inter TBs (off by default)")
     ap.add_argument("--av1-intra-blocks", dest="intra_in_inter", action="store_true",
                     help="AV1: 16x16 intra blocks in inter frames (off by default)")
     ap.add_argument("--av1-cfl", dest="cfl", action="store_true",
@@ -1108,6 +1110,7 @@ def main(argv=None) -> int:
                   tools={"wpp": a.wpp, "rqt": a.rqt, "pintra": a.pintra, "cascade": a.cascade, "rdoq": a.rdoq,
                          **({"subpel_satd": True} if a.subpel_satd else {}),
                          **({"sign_hiding": True} if a.sign_hiding else {}),
+                         **({"rd_quant": True} if a.rd_quant else {}),
                          **({"intra_in_inter": True} if a.intra_in_inter else {}),
                          **({"cfl": True} if a.cfl else {}),
                          **({"dir_intra": True} if a.dir_intra else {}),

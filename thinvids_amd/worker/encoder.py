@@ -56,6 +56,7 @@ class EncodeSpec:
     rdoq: bool = True  # inter TBs drop trailing lone-+-1 coefficient groups (tv/hevc_defs.h)
     subpel_satd: bool = False  # sub-pel motion vectors chosen by SATD + MV rate (tv/me_model.h)
     sign_hiding: bool = False  # sign data hiding: one sign per coefficient group in the parity (tv/sdh.h)
+    rd_quant: bool = False  # rate-distortion quantisation of inter TBs (tv/rdq.h)
     intra_in_inter: bool = False  # AV1: 16x16 intra blocks in inter frames (tv/av1_enc.h)
     cfl: bool = False  # AV1: chroma from luma in intra blocks (tv/av1_enc.h)
     dir_intra: bool = False  # AV1: directional intra angles with CDF-based mode rates (tv/av1_enc.h)
@@ -70,7 +71,7 @@ class EncodeSpec:
                     self.dir_intra, self.tx_split)
         return (self.width, self.height, self.qp, self.gop, self.search_range, self.deblock, self.sao, self.seed,
                 self.crf, self.hevc_bframes(), self.wpp, self.rqt, self.pintra, self.cascade, self.rdoq, self.entropy, self.subpel_satd,
-                self.sign_hiding)
+                self.sign_hiding, self.rd_quant)
 
     def tools(self) -> dict:
         """The coding-tool switches as GpuEngine / CpuEncoder keyword arguments."""
@@ -79,6 +80,8 @@ class EncodeSpec:
             t["subpel_satd"] = True
         if self.sign_hiding:
             t["sign_hiding"] = True
+        if self.rd_quant:
+            t["rd_quant"] = True
         if self.intra_in_inter and self.codec == "av1":  # an AV1 tool: never reaches the HEVC encoders
             t["intra_in_inter"] = True
         if self.cfl and self.codec == "av1":

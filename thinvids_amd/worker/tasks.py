@@ -108,6 +108,7 @@ def encode_spec_for_job(job: dict, settings: dict | None = None) -> EncodeSpec:
                       bframes=_pow2(as_int(job.get("bframes") or s.get("tv_bframes"), 1)),
                       subpel_satd=as_bool(job.get("subpel_satd") or s.get("tv_subpel_satd") or "0"),
                       sign_hiding=as_bool(job.get("sign_hiding") or s.get("tv_sign_hiding") or "0"),
+                      rd_quant=as_bool(job.get("rd_quant") or s.get("tv_rd_quant") or "0"),
                       intra_in_inter=as_bool(job.get("av1_intra_blocks") or s.get("tv_av1_intra_blocks") or "0"),
                       cfl=as_bool(job.get("av1_cfl") or s.get("tv_av1_cfl") or "0"),
                       dir_intra=as_bool(job.get("av1_dir_intra") or s.get("tv_av1_dir_intra") or "0"),

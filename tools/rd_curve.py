@@ -48,7 +48,8 @@ def run_point(args):
 
     uv_mse = []
     kw = dict(sao=a["sao"], rqt=a["rqt"], pintra=a["pintra"], wpp=a["wpp"], cascade=a["ippp_cascade"], rdoq=a["rdoq"],
-              subpel_satd=a["subpel_satd"], sign_hiding=a.get("sign_hiding", False))
+              subpel_satd=a["subpel_satd"], sign_hiding=a.get("sign_hiding", False),
+              rd_quant=a.get("rd_quant", False))
     if a.get("engine") == "gpu":
         return run_point_gpu(qp, a, w, h, seed, fq, kw)
     if a.get("codec") == "av1":
@@ -131,6 +132,7 @@ def main():
     ap.add_argument("--rdoq", type=int, default=1, help="RDOQ-lite coefficient-group trimming")
     ap.add_argument("--subpel-satd", type=int, default=0, help="sub-pel vectors chosen by SATD + MV rate (tv/me_model.h)")
     ap.add_argument("--sign-hiding", type=int, default=0, help="sign data hiding (tv/sdh.h)")
+    ap.add_argument("--rd-quant", type=int, default=0, help="rate-distortion quantisation of inter TBs (tv/rdq.h)")
     ap.add_argument("--intra-in-inter", type=int, default=0, help="av1: intra blocks in inter frames (tv/av1_enc.h)")
     ap.add_argument("--cfl", type=int, default=0, help="av1: chroma from luma (tv/av1_enc.h)")
     ap.add_argument("--dir-intra", type=int, default=0, help="av1: directional intra angles, CDF-based mode rates (tv/av1_enc.h)")
@@ -148,7 +150,7 @@ def main():
                cascade=[int(x) for x in a.cascade.split(",")] if a.cascade else [], iqp=a.iqp,
                bframes=a.bframes, codec=a.codec, rqt=bool(a.rqt), pintra=bool(a.pintra), wpp=bool(a.wpp),
                ippp_cascade=bool(a.ippp_cascade), rdoq=bool(a.rdoq), subpel_satd=bool(a.subpel_satd),
-               sign_hiding=bool(a.sign_hiding), intra_in_inter=bool(a.intra_in_inter), cut=a.cut,
+               sign_hiding=bool(a.sign_hiding), rd_quant=bool(a.rd_quant), intra_in_inter=bool(a.intra_in_inter), cut=a.cut,
                engine=a.engine, cfl=bool(a.cfl), dir_intra=bool(a.dir_intra), tx_split=bool(a.tx_split), fan=bool(a.fan), chroma_k=[int(x) for x in a.chroma_k.split(",")] if a.chroma_k else [])
     qps = [int(q) for q in a.qps.split(",")]
     if a.engine == "gpu":
